@@ -1,6 +1,6 @@
 """Benchmark of the MMDiT-B flow-matching TRAINING step on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: starts the N ranks itself, one child process per GPU)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]   (N > 1: starts the N ranks itself, one child process per GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One step = one optimizer step on one synthetic batch per GPU (per-GPU batch 64, weak scaling):
@@ -10,9 +10,17 @@ RCCL gradient all-reduce (N>1) -> unscale, clip(1.0), AdamW, scheduler.  Nothing
 Rank 0 prints ONE JSON line.  value = N * 64 * K / max-over-ranks wall time.
 
 Launch mode: after the warm-up the optimizer step (with its collectives) is captured into a hipGraph and the K timed steps are
-replays (one host call each); the same trainer's eager rate is measured first and reported as `ms_per_step_eager`; `--eager` times
+replays (one host call each); with --full the same trainer's eager rate is measured first and reported as `ms_per_step_eager`; `--eager` times
 host launches instead.  The line proves that the timed steps trained: every timed step's loss is cloned on the device and must lie in
 (1e-3, 10), the parameter norms must have moved (`loss_first`, `final_loss`, `param_norm_sum`); otherwise the run fails.
+
+A plain run sets up, warms up, captures, times the K steps and prints the line; everything else it can measure runs only with
+--full: the eager leg (`ms_per_step_eager`), `clocks`, `roofline`, the per-bucket collective timing (N > 1) and `cpu_baseline`
+(--no-eager-leg / --no-roofline / --no-cpu-baseline drop single parts of a --full run).
+--dump-outputs DIR: after the timed steps (before any --full extra), rank 0 writes what the last timed step returned to its caller
+-- its loss (loss.npy) and the parameters it left behind: every parameter's L2 norm in float64 (param_norms.npy, in
+named_parameters() order) and a fixed sample of up to 4096 elements per parameter in float32 (param_sample.npy, the same indices
+in every run: torch.Generator seeded 0).  Weights and data are seeded, so the same arguments give the same inputs in every run.
 
 roofline: the dominant kernel (by total time) is the MFMA GEMM; every GEMM launch of three extra
 steps after the timed region is bracketed with HIP events on its launch stream, achieved = its
@@ -106,6 +114,25 @@ def cpu_baseline(seconds_budget=25.0):
             "sample": f"{n} optimizer steps of MMDiT-B (fp32 weights, reference CPU attention branch), batch {bs}, fwd+bwd+clip+AdamW, torch CPU {threads} threads"}
 
 
+def dump_outputs(out_dir, loss, net, per_param=4096):
+    """DIR/loss.npy (float32), DIR/param_norms.npy (float64, one per parameter), DIR/param_sample.npy (float32, <= per_param elements per
+    parameter at indices drawn from a generator seeded 0: identical in every run).  MMDiT-B: 427 parameters, about 5.5 MB in all."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator().manual_seed(0)
+    norms, sample = [], []
+    with torch.no_grad():
+        for _, p in net.named_parameters():
+            flat = p.detach().reshape(-1)
+            norms.append(float(flat.double().norm()))
+            idx = torch.randint(0, flat.numel(), (per_param,), generator=g) if flat.numel() > per_param else torch.arange(flat.numel())
+            sample.append(flat[idx.to(flat.device)].float().cpu())
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray(float(loss), dtype=np.float32))
+    np.save(os.path.join(out_dir, "param_norms.npy"), np.asarray(norms, dtype=np.float64))
+    np.save(os.path.join(out_dir, "param_sample.npy"), torch.cat(sample).numpy().astype(np.float32))
+
+
 def self_launch(n):
     """Start one bench.py process per GPU (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment, what
     torch.distributed.run would set) and wait for them; rank 0's JSON line goes to this process's stdout.  Returns the exit
@@ -152,10 +179,16 @@ def main():
     ap.add_argument("--graph", action="store_true", help="(default) replay the optimizer step from a hipGraph captured after the warm-up; with this flag a failed capture is an error instead of an eager fallback")
     ap.add_argument("--eager", action="store_true", help="issue every launch of every step from the host")
     ap.add_argument("--no-eager-leg", action="store_true", help="profiling runs: skip the untimed-for-the-metric eager timing leg (ms_per_step_eager) in front of the capture")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: eager leg, clocks, roofline, collective timing, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's loss and (a fixed sample of) the parameters it produced as DIR/<name>.npy")
     ap.add_argument("--precision", default="fast", choices=["fast", "parity"], help="development: parity = the 1e-3 mode (fp32 activations, 3-term split-bf16 GEMMs, "
                     "reference rounding points in attention); the headline metric is quoted on fast (= the reference's bf16 autocast)")
     ap.add_argument("--check-launch", action="store_true", help="rendezvous check only (gloo, no GPU): every rank joins the group, one all-reduce, rank 0 prints the world size")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:       # a plain run: only what the headline figure needs
+        args.no_eager_leg, args.no_roofline, args.no_cpu_baseline = True, True, True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher.  Nothing in this process has touched the GPU yet (no torch import,
@@ -294,6 +327,8 @@ def main():
     # the line must prove that the timed steps trained: a finite, plausible loss in every timed step and parameters that moved
     if not all(loss_is_plausible(l, BENCH_WINDOW) for l in losses) or check1 == check0:
         raise RuntimeError(f"bench: the timed steps did not train (losses {[float(l) for l in losses]}, parameter norm sum {check0} -> {check1})")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, losses[-1], net)
 
     # shader clock and board power under the step (sysfs hwmon of this GPU, polled from a thread over extra UNTIMED steps in the launch mode of the
     # timed ones): the MFMA peak of the roofline is quoted at 2.4 GHz, the GEMMs run at the board's power limit and clock lower

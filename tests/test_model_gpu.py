@@ -257,7 +257,10 @@ def test_gradients_fast_mode_vs_oracle_autograd(cname, h, w):
     oracle's own fp32-vs-float64 distance) -- and the numbers measured here: tensors <= 7.4e-3 at B depth, <= 6.7e-3 at micro / XS): every tensor
     parameter rel-L2 < 2e-2 at B depth, 1.5e-2 through 2-3 blocks; the three scalar parameters (heavily cancelling sums over the whole text /
     time path: measured 7.3e-2 / 9.4e-3 at B, <= 5e-2 at micro / XS) < max(1e-1, 2 x the oracle's own fp32-vs-float64 distance), never more than
-    3e-1.  (Against the oracle WITHOUT gradient rounding learnable_scalar read 2.8e-1 at B depth: most of that was the comparator.)"""
+    3e-1.  (Against the oracle WITHOUT gradient rounding learnable_scalar read 2.8e-1 at B depth: most of that was the comparator.)
+    At B depth the scalars are compared with the float64 oracle, and the oracle's own distance is the largest of its fp32 run and three float64
+    runs on inputs jittered by 2^-20 (relative): the fp32 oracle's value of learnable_scalar depends on the host's BLAS reduction order (on one
+    host 2e-2 ... 1.7e-1 from float64 over 1-16 threads, on another 2.8e-3 at every thread count), a yardstick that must not depend on the host."""
     x, c, cp = make_inputs(6, 2, h, w, text_scale=30.0)
     t = torch.tensor([0.35, 0.8])
     net, sd = build(cname, precision="fast")
@@ -271,19 +274,34 @@ def test_gradients_fast_mode_vs_oracle_autograd(cname, h, w):
     # The three scalar parameters are sums with heavy cancellation over the whole text path (learnable_scalar: sum over B x 77 x 2304 products
     # of the gradient that has come back through every block); at B depth their error is rounding noise amplified by that cancellation.  The
     # yardstick: how far the ORACLE's own gradient of the scalar moves when it is run in exact (float64) arithmetic between the same rounding
-    # points (round 5, with gradient rounding: learnable_scalar 7.0e-2, learnable_scalar2 1.4e-2, time_scale 4.0e-3).
-    floor = {}
+    # points (round 5, with gradient rounding: learnable_scalar 7.0e-2, learnable_scalar2 1.4e-2, time_scale 4.0e-3).  That distance is set by
+    # the host's fp32 reduction order, so at B depth the scalars are compared with the float64 oracle itself, and the yardstick also takes how far
+    # the float64 gradient moves when the inputs move by 2^-20 (relative, about the fp32 accumulation error of a K = 768 ... 3072 dot product):
+    # rounding points that flip under that much noise are what any fp32 evaluation (the HIP path's, the oracle's) can land on either side of.
+    floor, exact = {}, {}
     if cname == "b":
-        sd64 = {k: (val.double().clone().requires_grad_(not k.endswith("freqs")) if val.is_floating_point() else val) for k, val in sd.items()}
-        O.forward(sd64, O.OracleConfig(**CONFIGS[cname], attn_core="flash_bf16", gemm="bf16", grad_round=True, dtype=torch.float64), x.double(), t.double(), c.double(), cp.double()).pow(2).mean().backward()
-        floor = {n: rel(sdr[n].grad, sd64[n].grad) for n, p in net.named_parameters() if p.requires_grad and p.numel() == 1}
+        def oracle64(seed):
+            g = torch.Generator().manual_seed(seed)
+            jit = (lambda a: a.double() * (1 + 2.0 ** -20 * torch.randn(a.shape, generator=g, dtype=torch.float64))) if seed else (lambda a: a.double())
+            s64 = {k: (val.double().clone().requires_grad_(not k.endswith("freqs")) if val.is_floating_point() else val) for k, val in sd.items()}
+            O.forward(s64, O.OracleConfig(**CONFIGS[cname], attn_core="flash_bf16", gemm="bf16", grad_round=True, dtype=torch.float64),
+                      jit(x), t.double(), jit(c), jit(cp)).pow(2).mean().backward()
+            return s64
+        scalars = [n for n, p in net.named_parameters() if p.requires_grad and p.numel() == 1]
+        sd64 = oracle64(0)
+        exact = {n: sd64[n].grad for n in scalars}
+        floor = {n: rel(sdr[n].grad, exact[n]) for n in scalars}
         print(f"[grads fast] {cname}: oracle fp32 vs float64 distance of the scalar parameters: " + ", ".join(f"{n} {v:.2e}" for n, v in floor.items()))
+        for seed in (1, 2, 3):
+            moved = oracle64(seed)
+            floor = {n: max(floor[n], rel(moved[n].grad, exact[n])) for n in scalars}
+        print(f"[grads fast] {cname}: with the float64 oracle on jittered inputs: " + ", ".join(f"{n} {v:.2e}" for n, v in floor.items()))
     res = []
     for n, p in net.named_parameters():
         if not p.requires_grad:
             assert p.grad is None
             continue
-        res.append((rel(p.grad, sdr[n].grad), n, p.numel()))
+        res.append((rel(p.grad, exact.get(n, sdr[n].grad)), n, p.numel()))
     res.sort(reverse=True)
     print(f"[grads fast] {cname}: {len(res)} parameters, worst per-parameter rel-L2 = {res[0][0]:.3e}, median {res[len(res) // 2][0]:.3e}")
     for r, n, k in res[:6]:

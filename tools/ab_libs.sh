@@ -6,7 +6,7 @@ for round in 1 2; do
   for v in "$@"; do
     if [ "$v" = default ]; then unset MMDIT_LIB; else export MMDIT_LIB=$GRAFT_REPO_ROOT/tools/scratch/$v/libmmdit_hip.so; fi
     echo "== round $round variant $v"
-    python bench.py --no-cpu-baseline --no-roofline 2>/dev/null | python -c "import sys, json; d = json.loads(sys.stdin.read()); print('bench', d['value'], 'img/s', d['ms_per_step'], 'ms/step  eager', d['ms_per_step_eager'], ' loss', d['final_loss'])"
+    python bench.py --full --no-cpu-baseline --no-roofline 2>/dev/null | python -c "import sys, json; d = json.loads(sys.stdin.read()); print('bench', d['value'], 'img/s', d['ms_per_step'], 'ms/step  eager', d['ms_per_step_eager'], ' loss', d['final_loss'])"
     if [ $round = 1 ]; then
       python tools/gemm_bench.py 2>&1 | grep "grouped\|square\|SwiGLU"
       python tools/attn_bench.py 30 2>&1 | grep "attn fwd"

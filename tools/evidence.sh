@@ -1,5 +1,6 @@
 cd $GRAFT_REPO_ROOT; R=$1
-python bench.py > gpurun_out/${R}_bench_line.json 2> gpurun_out/${R}_bench.err
+EVIDENCE_OUT=${EVIDENCE_OUT:-evidence_out}; mkdir -p "$EVIDENCE_OUT"     # where the full bench line (--full: roofline, clocks, eager rate, cpu_baseline) goes
+python bench.py --full > "$EVIDENCE_OUT/${R}_bench_line.json" 2> "$EVIDENCE_OUT/${R}_bench.err"
 cd /tmp; export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 rocprofv3 --kernel-trace -d gpurun_out/prof_$R -o run -- python3 bench.py --steps 10 --warmup 1 --no-cpu-baseline --no-roofline --no-eager-leg > gpurun_out/${R}_prof.log 2>&1
 DB=$(find gpurun_out/prof_$R -name "*.db" | head -1)
