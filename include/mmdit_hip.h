@@ -436,6 +436,15 @@ int mmdit_vae_pad_cast(const void* x, int x_dtype, int batch, int H, int W, int 
 /* y = softmax(scale * x) over the first `cols` entries of each row (pitch ld, padding written as 0), fp32 -> bf16
  * (single-head mid-block attention, attention_processor.py). */
 int mmdit_vae_softmax_rows(const float* x, int rows, int cols, int ld, float scale, void* y_bf16, mmdit_stream_t stream);
+/* Mid-block self-attention of the VAE (the diffusers `Attention` inside AutoencoderKL's mid block: one head of width C), the whole
+ * batch in one launch:  O[b] = softmax(scale * Q[b] K[b]^T) V[b], non-causal, forward only, no score matrix in memory.
+ * Q, K, V: bf16 rows (batch * tokens, C) with row pitch ld >= C elements, ld % 8 == 0, 16-byte aligned (column slices of one
+ * projection matrix qualify); image b owns rows [b * tokens, (b + 1) * tokens).  O: bf16 (batch * tokens, C), contiguous.
+ * fp32 scores and online softmax, P rounded to bf16 for the second MFMA, fp32 accumulation, one division by the fp32 row sum.
+ * Any tokens >= 1: keys of the partial last tile are masked and their V rows contribute exactly zero; no load leaves the operands.
+ * Deterministic (no atomics, no workspace).  C != 512, a bad ld or tokens < 1: MMDIT_ERR_SHAPE, nothing is launched. */
+int mmdit_vae_attn_fwd(const void* Q, const void* K, const void* V, int ld, int batch, int tokens, int C,
+                       float scale, void* O_bf16, mmdit_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Optimizer step: GradScaler.unscale_ + torch.nn.utils.clip_grad_norm_ + AdamW.step of the reference

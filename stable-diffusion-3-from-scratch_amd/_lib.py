@@ -129,6 +129,7 @@ _SIGNATURES = {
     "mmdit_vae_groupnorm": ([_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, ctypes.c_float, _i, _vp, _vp, _i, _vp], _i),
     "mmdit_vae_pad_cast": ([_vp, _i, _i, _i, _i, _i, _i, _vp, _vp], _i),
     "mmdit_vae_softmax_rows": ([_vp, _i, _i, _i, ctypes.c_float, _vp, _vp], _i),
+    "mmdit_vae_attn_fwd": ([_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp], _i),
     "mmdit_patchify": ([_vp, _i, _i, _i, _i, _i, _vp, _i, _vp], _i),
     "mmdit_unpatchify": ([_vp, _i, _i, _i, _i, _i, _vp, _i, _vp], _i),
     "mmdit_time_embed_fwd": ([_vp, _vp, _vp, _i, _i, _vp, _i, _vp], _i),

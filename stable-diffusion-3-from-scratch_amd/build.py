@@ -14,9 +14,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmmdit_hip.so")
 HEADER = os.path.join(HERE, "..", "include", "mmdit_hip.h")
-SOURCES = ["gemm.hip", "gemm_dma.hip", "gemm_lean.hip", "gemm8p.hip", "gemm8p_inf.hip", "rowops.hip", "attention.hip", "vae.hip", "optim.hip"]
+SOURCES = ["gemm.hip", "gemm_dma.hip", "gemm_lean.hip", "gemm8p.hip", "gemm8p_inf.hip", "rowops.hip", "attention.hip", "vae.hip", "vae_attn.hip", "optim.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + os.environ.get("MMDIT_EXTRA_HIPCC_FLAGS", "").split()
+# per-source flags.  vae_attn.hip: its 128 output accumulators are rescaled by the VALU, so they must live in the VGPR half of the register
+# file (the default AGPR form copies all of them to VGPRs and back in every iteration); the Q fragments take the AGPR half instead
+SOURCE_FLAGS = {"vae_attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 
 def _sha(paths, extra=""):
@@ -40,7 +43,7 @@ def source_hash(src):
     headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [HEADER]
     if src == "gemm8p_inf.hip":
         headers.append(os.path.join(CSRC, "gemm8p.hip"))      # (it is that file, compiled with MMDIT_G8_PART 2)
-    return _sha([os.path.join(CSRC, src)] + headers, " ".join([HIPCC] + FLAGS))
+    return _sha([os.path.join(CSRC, src)] + headers, " ".join([HIPCC] + FLAGS + SOURCE_FLAGS.get(src, [])))
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -50,7 +53,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         obj = os.path.join(CSRC, src.replace(".hip", ".o"))
         if not force and os.path.exists(obj) and _read(obj + ".sha") == want[src]:
             return obj, False
-        cmd = [HIPCC] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj]
+        cmd = [HIPCC] + FLAGS + SOURCE_FLAGS.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)

@@ -817,3 +817,29 @@ def vae_softmax_rows(x, scale, cols=None):
     out = torch.empty((rows, ld), dtype=torch.bfloat16, device=x.device)
     check(_lib.lib().mmdit_vae_softmax_rows(_p(_c(x)), rows, cols, ld, float(scale), _p(out), _s()), "mmdit_vae_softmax_rows")
     return out
+
+
+def _rows_ld(t, C, what):
+    """Row pitch of a bf16 (rows, C) operand: contiguous, or a column slice of a contiguous matrix."""
+    if not t.is_cuda:
+        raise RuntimeError("mmdit HIP op called with a CPU tensor: the MMDiT hot path has no CPU fallback")
+    if t.dtype != torch.bfloat16 or t.dim() != 2 or t.shape[1] != C:
+        raise RuntimeError(f"{what} must be a bf16 (rows, {C}) tensor")
+    if t.stride(1) != 1 or t.stride(0) < C or t.stride(0) % 8 or t.data_ptr() % 16:
+        raise RuntimeError(f"{what} must be contiguous or a 16-byte aligned column slice of a contiguous matrix")
+    return t.stride(0)
+
+
+def vae_attention(q, k, v, batch, tokens, scale):
+    """Single-head softmax attention of the VAE mid block, the whole batch in one launch (csrc/vae_attn.hip).
+    q, k, v: bf16 (batch * tokens, 512), contiguous or column slices of one contiguous matrix (same row pitch); image b owns rows
+    [b * tokens, (b + 1) * tokens).  Returns bf16 (batch * tokens, 512)."""
+    C = q.shape[1]
+    ld = _rows_ld(q, C, "q")
+    if _rows_ld(k, C, "k") != ld or _rows_ld(v, C, "v") != ld:
+        raise RuntimeError("q, k and v must share one row pitch")
+    if not (q.shape[0] == k.shape[0] == v.shape[0] == batch * tokens):
+        raise RuntimeError(f"q, k and v need batch * tokens = {batch * tokens} rows")
+    out = torch.empty((batch * tokens, C), dtype=torch.bfloat16, device=q.device)
+    check(_lib.lib().mmdit_vae_attn_fwd(_p(q), _p(k), _p(v), ld, batch, tokens, C, float(scale), _p(out), _s()), "mmdit_vae_attn_fwd")
+    return out

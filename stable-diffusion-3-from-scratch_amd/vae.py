@@ -7,7 +7,8 @@ Mirror of the diffusers interface that those call sites touch: `.config.{latent_
 (a real `diffusion_pytorch_model.safetensors` loads with `load_state_dict`).  Every 3x3 convolution is an implicit GEMM
 inside the LDS-DMA MFMA kernel (zero-bordered NHWC bf16 operand, bf16 operands, fp32 accumulate; conv_in with its 3 / 16
 channels zero-padded to 64), GroupNorm+SiLU a statistics pass + an apply pass that writes the next convolution's operand,
-the mid-block attention GEMM + row softmax + GEMM.  No CPU / PyTorch-math fallback."""
+the mid-block attention one batched flash kernel at head width 512 (csrc/vae_attn.hip: no score matrix in memory, any token count; other
+widths run per image as GEMM + row softmax + GEMM).  No CPU / PyTorch-math fallback."""
 import math
 from types import SimpleNamespace
 
@@ -24,6 +25,7 @@ def _pad8(n):
 
 
 _H_BF16 = _lib.experiment("MMDIT_VAE_H_BF16", "1") != "0"     # A/B switch: conv1 outputs of the ResNet blocks in bf16
+_ATTN_FUSED = _lib.experiment("MMDIT_VAE_ATTN", "fused") != "gemm"   # A/B switch: "gemm" = the per-image GEMM + row softmax + GEMM path
 _CIN_PAD = 64     # conv_in operand channels (the implicit-GEMM K = 9 * C must be a multiple of the 64-wide K tile)
 
 
@@ -234,6 +236,9 @@ class AutoencoderKL(nn.Module):
         q = ops.gemm(h, wq, bias=bq, out_dtype=BF16)
         k = ops.gemm(h, wk, bias=bk, out_dtype=BF16)
         v = ops.gemm(h, wv, bias=bv, out_dtype=BF16)
+        if C == 512 and _ATTN_FUSED:    # one head of width 512: one flash launch for the whole batch
+            o = ops.vae_attention(q, k, v, B, HW, 1.0 / math.sqrt(C))
+            return _Act(ops.gemm(o, wo, bias=bo, residual=a.x, out_dtype=F32), a.B, a.H, a.W)
         o = torch.empty((B * HW, C), dtype=BF16, device=h.device)
         HWp = _pad8(HW)         # GEMM operands need 16-byte rows: keys / values are zero-padded to a multiple of 8 tokens
         kp, vp = torch.zeros((HWp, C), dtype=BF16, device=h.device), torch.zeros((HWp, C), dtype=BF16, device=h.device)
