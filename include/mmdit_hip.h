@@ -329,6 +329,17 @@ int mmdit_qk_norm_rope_fwd_pair(const mmdit_qk_problem* p0, const mmdit_qk_probl
                                 void* Q, void* K, void* V, mmdit_stream_t stream);
 int mmdit_qk_norm_rope_bwd_pair(const mmdit_qk_problem* p0, const mmdit_qk_problem* p1, const void* dQ, const void* dK, const void* dV, int dq_dtype,
                                 int qkv_dtype, int dqkv_dtype, int batch, int heads, int s_total, mmdit_stream_t stream);
+/* kv_merge_attn (Attention.py:243-251): the same launches with the keys and values of adjacent token pairs averaged.  After the norm and
+ * (image stream) the rotation of EACH token in fp32, K'[j] = (K[2j] + K[2j+1]) / 2 is rounded to bf16 once; V'[j] = (V[2j] + V[2j+1]) / 2 of
+ * the raw rows.  Pairs are adjacent in the flattened token order of their stream.  Q (batch, heads, s_total, 64) is written as by
+ * mmdit_qk_norm_rope_fwd_pair, bit for bit; K and V are (batch, heads, s_total / 2, 64), pair j of a stream at row tok0 / 2 + j.
+ * bwd: dQ (batch, heads, s_total, 64), dK / dV (batch, heads, s_total / 2, 64): every token of a pair receives half of its merged row's
+ * gradient, pushed through that token's own RoPE / norm backward; dqkv rows and the accumulated dwq / dwk as in mmdit_qk_norm_rope_bwd_pair.
+ * An odd tokens, tok0 or s_total: MMDIT_ERR_SHAPE, nothing is launched.  heads <= 21 (one pair per workgroup of 24 * heads <= 512 threads). */
+int mmdit_qk_norm_rope_fwd_merge_pair(const mmdit_qk_problem* p0, const mmdit_qk_problem* p1, int qkv_dtype, int batch, int heads, int s_total,
+                                      void* Q, void* K, void* V, mmdit_stream_t stream);
+int mmdit_qk_norm_rope_bwd_merge_pair(const mmdit_qk_problem* p0, const mmdit_qk_problem* p1, const void* dQ, const void* dK, const void* dV, int dq_dtype,
+                                      int qkv_dtype, int dqkv_dtype, int batch, int heads, int s_total, mmdit_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Joint softmax attention core, non-causal, head_dim 64, bf16 operands, fp32 accumulate.
@@ -357,6 +368,16 @@ int mmdit_attn_bwd(const void* Q, const void* K, const void* V, const void* Ox, 
                    const void* dOx, const void* dOc, const float* lse, float* delta,
                    int batch, int heads, int S, int n_img, float scale,
                    void* dQ, void* dK, void* dV, int dq_dtype, mmdit_stream_t stream);
+/* The same attention with a key length of its own (Attention.py:243-251, kv_merge_attn: S queries against the s_kv = S / 2 pair-averaged
+ * keys and values of mmdit_qk_norm_rope_fwd_merge_pair).  Q, dQ: (batch, heads, S, 64); K, V, dK, dV: (batch, heads, s_kv, 64); Ox / Oc / lse /
+ * delta and the n_img split are query-side and keep their shapes.  Any 1 <= s_kv <= S (else MMDIT_ERR_SHAPE, nothing is launched); keys of
+ * the partial last tile are masked, no load leaves the operands.  s_kv == S: the results of mmdit_attn_fwd / mmdit_attn_bwd, bit for bit. */
+int mmdit_attn_fwd_kv(const void* Q, const void* K, const void* V, int batch, int heads, int S, int s_kv, int n_img,
+                      float scale, int mode, void* Ox, void* Oc, float* lse, mmdit_stream_t stream);
+int mmdit_attn_bwd_kv(const void* Q, const void* K, const void* V, const void* Ox, const void* Oc,
+                      const void* dOx, const void* dOc, const float* lse, float* delta,
+                      int batch, int heads, int S, int s_kv, int n_img, float scale,
+                      void* dQ, void* dK, void* dV, int dq_dtype, mmdit_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * MLP activations.  swiglu: h = silu(g) * u with [g | u] = gu (rows, 2*hidden)  (xformers SwiGLU

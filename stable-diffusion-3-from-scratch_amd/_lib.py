@@ -104,6 +104,8 @@ _SIGNATURES = {
     "mmdit_ln_modulate_bwd_pair": ([ctypes.POINTER(LnBwdProblem), ctypes.POINTER(LnBwdProblem), _i, _i, _vp], _i),
     "mmdit_qk_norm_rope_fwd_pair": ([ctypes.POINTER(QkProblem), ctypes.POINTER(QkProblem), _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "mmdit_qk_norm_rope_bwd_pair": ([ctypes.POINTER(QkProblem), ctypes.POINTER(QkProblem), _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
+    "mmdit_qk_norm_rope_fwd_merge_pair": ([ctypes.POINTER(QkProblem), ctypes.POINTER(QkProblem), _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "mmdit_qk_norm_rope_bwd_merge_pair": ([ctypes.POINTER(QkProblem), ctypes.POINTER(QkProblem), _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "mmdit_mlp_act_bwd_pair": ([ctypes.POINTER(MlpBwdProblem), ctypes.POINTER(MlpBwdProblem), _i, _i, _i, _vp], _i),
     "mmdit_gate_residual_fwd": ([_vp, _vp, _i, _vp, _i64, _i, _i, _i, _vp, _vp], _i),
     "mmdit_ln_modulate_bwd": ([_vp, _i, _vp, _vp, _vp, _vp, _i64, _vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp], _i),
@@ -115,6 +117,8 @@ _SIGNATURES = {
     "mmdit_attn_fwd": ([_vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp], _i),
     "mmdit_attn_bwd_qk": ([_vp] * 9 + [_i, _i, _i, _i, _f] + [_vp] * 11 + [_vp], _i),
     "mmdit_attn_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp], _i),
+    "mmdit_attn_fwd_kv": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp], _i),
+    "mmdit_attn_bwd_kv": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp], _i),
     "mmdit_swiglu_fwd": ([_vp, _vp, _i, _i, _i, _vp], _i),
     "mmdit_swiglu_bwd": ([_vp, _vp, _vp, _i, _i, _i, _vp, _vp], _i),
     "mmdit_gelu_fwd": ([_vp, _vp, _i, _i, _i, _vp], _i),

@@ -1,8 +1,9 @@
 """Joint image+text attention: mirror of the reference's src/blocks/Attention.py for the trained
 configuration (dual stream, attn_type softmax / softmax_flash, RoPE2d, non-causal; ctor 16-114,
 forward 118-135, 174-194, 258-293, 410-425).  Experimental attention types of the reference
-(cosine*, relu, silu, exp, both, kv_merge_attn, qk_half_dim, 1-D RoPE, RoPE2dV2) are out of scope and
-raise."""
+(cosine*, relu, silu, exp, both, qk_half_dim, 1-D RoPE, RoPE2dV2) are out of scope and
+raise.  kv_merge_attn (243-251) is implemented: the keys / values of adjacent token pairs of each stream are
+averaged (mmdit_qk_norm_rope_fwd_merge_pair) and S queries attend to S / 2 keys (mmdit_attn_fwd_kv)."""
 from types import SimpleNamespace as NS
 
 import torch
@@ -27,10 +28,16 @@ class _AttentionFn(torch.autograd.Function):
         qkv_x = ops.gemm(xa, w.Wqkv_x, out_dtype=m.T, precision=m.prec)
         qkv_c = ops.gemm(ca, w.Wqkv_c, out_dtype=m.T, precision=m.prec)
         Q = torch.empty((B, H, S, 64), dtype=BF16, device=dev)
-        K, V = torch.empty_like(Q), torch.empty_like(Q)
-        ops.qk_norm_rope_fwd(qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], B, N, H, S, 0, Q, K, V)
-        ops.qk_norm_rope_fwd(qkv_c, w.wq_c, w.wk_c, None, None, B, Mt, H, S, N, Q, K, V)
-        Ox, Oc, lse = ops.attn_fwd(Q, K, V, N, mod.scale, m.attn_mode)
+        if mod.kv_merge_attn:
+            mod._check_even(N, Mt)
+            K, V = torch.empty((B, H, S // 2, 64), dtype=BF16, device=dev), torch.empty((B, H, S // 2, 64), dtype=BF16, device=dev)
+            ops.qk_norm_rope_fwd_merge_pair((qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], N, 0), (qkv_c, w.wq_c, w.wk_c, None, None, Mt, N), B, H, S, Q, K, V)
+            Ox, Oc, lse = ops.attn_fwd(Q, K, V, N, mod.scale, m.attn_mode, s_kv=S // 2)
+        else:
+            K, V = torch.empty_like(Q), torch.empty_like(Q)
+            ops.qk_norm_rope_fwd(qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], B, N, H, S, 0, Q, K, V)
+            ops.qk_norm_rope_fwd(qkv_c, w.wq_c, w.wk_c, None, None, B, Mt, H, S, N, Q, K, V)
+            Ox, Oc, lse = ops.attn_fwd(Q, K, V, N, mod.scale, m.attn_mode)
         Oxa = m.act(Ox.view(B * N, d))
         out_x = ops.gemm(Oxa, w.Wo_x, out_dtype=F32, precision=m.prec).view(B, N, d)
         if mod.last:
@@ -59,10 +66,15 @@ class _AttentionFn(torch.autograd.Function):
             dac = m.act(doc.reshape(B * Mt, d).contiguous())
             dOc = ops.gemm(dac, w.Wo_c, b_kmajor=True, out_dtype=BF16, precision=m.prec)
             mod._po_c.split_grad(ops.gemm(dac, Oca, a_kmajor=True, b_kmajor=True, out_dtype=F32, precision=m.prec), gout)
-        dQ, dK, dV = ops.attn_bwd(Q, K, V, Ox, Oc, dOx, dOc, lse, N, mod.scale, m.T)
         gq_x, gk_x, gq_c, gk_c = [torch.zeros(64, dtype=F32, device=dev) for _ in range(4)]
-        dqkv_x = ops.qk_norm_rope_bwd(dQ, dK, dV, qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], B, N, H, S, 0, gq_x, gk_x, m.T)
-        dqkv_c = ops.qk_norm_rope_bwd(dQ, dK, dV, qkv_c, w.wq_c, w.wk_c, None, None, B, Mt, H, S, N, gq_c, gk_c, m.T)
+        if mod.kv_merge_attn:
+            dQ, dK, dV = ops.attn_bwd(Q, K, V, Ox, Oc, dOx, dOc, lse, N, mod.scale, m.T, s_kv=S // 2)
+            dqkv_x, dqkv_c = ops.qk_norm_rope_bwd_merge_pair(dQ, dK, dV, (qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], N, 0, gq_x, gk_x),
+                                                             (qkv_c, w.wq_c, w.wk_c, None, None, Mt, N, gq_c, gk_c), B, H, S, m.T)
+        else:
+            dQ, dK, dV = ops.attn_bwd(Q, K, V, Ox, Oc, dOx, dOc, lse, N, mod.scale, m.T)
+            dqkv_x = ops.qk_norm_rope_bwd(dQ, dK, dV, qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], B, N, H, S, 0, gq_x, gk_x, m.T)
+            dqkv_c = ops.qk_norm_rope_bwd(dQ, dK, dV, qkv_c, w.wq_c, w.wk_c, None, None, B, Mt, H, S, N, gq_c, gk_c, m.T)
         dx = ops.gemm(dqkv_x, w.Wqkv_x, b_kmajor=True, out_dtype=F32, precision=m.prec).view(B, N, d)
         dc = ops.gemm(dqkv_c, w.Wqkv_c, b_kmajor=True, out_dtype=F32, precision=m.prec).view(B, Mt, d)
         mod._pqkv_x.split_grad(ops.gemm(dqkv_x, xa, a_kmajor=True, b_kmajor=True, out_dtype=F32, precision=m.prec), gout)
@@ -78,7 +90,7 @@ class Attention(nn.Module):
         super().__init__()
         if attn_type not in ("softmax", "softmax_flash"):
             raise RuntimeError(f"attn_type must be 'softmax' or 'softmax_flash' on the HIP path, but got {attn_type}")
-        if not dual or causal or kv_merge_attn or qk_half_dim or emb_dim is not None:
+        if not dual or causal or qk_half_dim or emb_dim is not None:
             raise RuntimeError("Attention: only the dual-stream, non-causal configuration of the trained model is implemented")
         if positional_encoding != "RoPE2d":
             raise RuntimeError("Attention: only positional_encoding='RoPE2d' is implemented")
@@ -114,6 +126,12 @@ class Attention(nn.Module):
     def _mode(self):
         return engine.FAST if self.precision == "fast" else engine.PARITY
 
+    @staticmethod
+    def _check_even(n_img, n_txt):
+        # (the reference asserts the same, Attention.py:246-247)
+        assert n_img % 2 == 0, "Merge attention requires an even number of keys"
+        assert n_txt % 2 == 0, "Merge attention requires an even number of keys"
+
     def _param_list(self):
         return [p for p in self.parameters() if p.requires_grad]
 
@@ -121,7 +139,7 @@ class Attention(nn.Module):
         return NS(Wqkv_x=self._pqkv_x.get(m), Wqkv_c=self._pqkv_c.get(m), Wo_x=self._po_x.get(m),
                   Wo_c=None if self.last else self._po_c.get(m),
                   wq_x=self.q_norm_x.weight.detach(), wk_x=self.k_norm_x.weight.detach(),
-                  wq_c=self.q_norm_c.weight.detach(), wk_c=self.k_norm_c.weight.detach())
+                  wq_c=self.q_norm_c.weight.detach(), wk_c=self.k_norm_c.weight.detach(), kv_merge=bool(self.kv_merge_attn))
 
     def scatter_grads(self, g, out: dict):
         self._pqkv_x.split_grad(g.Wqkv_x, out)

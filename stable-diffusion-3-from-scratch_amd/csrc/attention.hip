@@ -276,10 +276,13 @@ __device__ __forceinline__ void rows_from_tile(const float* tile, int lane, int 
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
-template <int NW, bool ORACLE>
+// KVL (mmdit_attn_fwd_kv / mmdit_attn_bwd_kv, Attention.py:243-251): K and V have s_kv rows of their own (pair-averaged keys: s_kv = S / 2); every
+// key-side bound below is Skv, every query-side one S.  KVL = false: Skv IS S at compile time -- the instantiations of the other entry points.
+template <int NW, bool ORACLE, bool KVL = false>
 __global__ __launch_bounds__(NW * 64) void attn_fwd_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
                                                             int BH, int H, int S, int n_img, float scale,
-                                                            bf16_t* __restrict__ Ox, bf16_t* __restrict__ Oc, float* __restrict__ lse) {
+                                                            bf16_t* __restrict__ Ox, bf16_t* __restrict__ Oc, float* __restrict__ lse, int s_kv = 0) {
+  const int Skv = KVL ? s_kv : S;
   constexpr int NT = NW * 64;
   __shared__ __attribute__((aligned(16))) char smem[2 * KT * P144 + 2 * KT * P192];
   auto kt = [&](int i) { return smem + i * KT * P144; };
@@ -292,8 +295,8 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_kernel(const bf16_t* __restr
   const int h = bh % H;
   const int64_t b = bh / H;
   const bf16_t* Qb = Q + (int64_t)bh * S * HD;
-  const bf16_t* Kb = K + (int64_t)bh * S * HD;
-  const bf16_t* Vb = V + (int64_t)bh * S * HD;
+  const bf16_t* Kb = K + (int64_t)bh * Skv * HD;
+  const bf16_t* Vb = V + (int64_t)bh * Skv * HD;
   const int q = qtile * 32 * NW + wave * 32 + (lane & 31);
   const int qc = min(q, S - 1);
   const bool active = qtile * 32 * NW + wave * 32 < S;   // wave-uniform: a wave whose 32 queries are all padding only helps with the tile copies
@@ -308,14 +311,14 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_kernel(const bf16_t* __restr
 #pragma unroll
     for (int r = 0; r < 16; r++) o[db][r] = 0.f;
   float m = -INFINITY, l = 0.f;
-  const int nkv = (S + KT - 1) / KT;
+  const int nkv = (Skv + KT - 1) / KT;
   u32x4 sk[tile_chunks<NT>()], sv[tile_chunks<NT>()];
 
   // scores of tile j from LDS buffer kb_ -> s[2] (masked keys = -inf).  fast: log2 domain; oracle: natural, bf16-rounded
   auto scores = [&](int j, const char* ktile, f32x16 (&s)[2]) {
 #pragma unroll
     for (int kb = 0; kb < 2; kb++) {
-      if (j * KT + kb * 32 >= S) {   // (wave-uniform) the whole 32-key block is padding: no MFMAs, all scores masked
+      if (j * KT + kb * 32 >= Skv) {   // (wave-uniform) the whole 32-key block is padding: no MFMAs, all scores masked
 #pragma unroll
         for (int r = 0; r < 16; r++) s[kb][r] = -INFINITY;
         continue;
@@ -328,10 +331,10 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_kernel(const bf16_t* __restr
 #pragma unroll
         for (int r = 0; r < 16; r++) s[kb][r] = bf2f(f2bf(bf2f(f2bf(s[kb][r])) * scale));   // Attention.py:277: bf16 matmul, then bf16 * scale
       }
-      if ((j + 1) * KT > S) {   // only the last (ragged) tile has keys to mask: wave-uniform branch
+      if ((j + 1) * KT > Skv) {   // only the last (ragged) tile has keys to mask: wave-uniform branch
 #pragma unroll
         for (int r = 0; r < 16; r++)
-          if (j * KT + kb * 32 + acc_row(r, lane) >= S) s[kb][r] = -INFINITY;
+          if (j * KT + kb * 32 + acc_row(r, lane) >= Skv) s[kb][r] = -INFINITY;
       }
     }
   };
@@ -346,7 +349,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_kernel(const bf16_t* __restr
   auto pv = [&](int j, const f32x16 (&p)[2], const char* vtile) {
 #pragma unroll
     for (int kb = 0; kb < 2; kb++)
-      if (j * KT + kb * 32 < S)   // (the probabilities of a padding block are all zero)
+      if (j * KT + kb * 32 < Skv)   // (the probabilities of a padding block are all zero)
 #pragma unroll
       for (int h8 = 0; h8 < 2; h8++) {
         const bf16x8 pf = pack_frag(p[kb], h8);
@@ -356,8 +359,8 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_kernel(const bf16_t* __restr
   };
 
   for (int pass = 0; pass < (ORACLE ? 2 : 1); pass++) {
-    tile_g2r<NT>(sk, Kb, 0, S, tid);
-    tile_g2r<NT>(sv, Vb, 0, S, tid);
+    tile_g2r<NT>(sk, Kb, 0, Skv, tid);
+    tile_g2r<NT>(sv, Vb, 0, Skv, tid);
     __syncthreads();  // previous pass done with the buffers
     tile_r2s<NT>(sk, kt(0), P144, tid);
     tile_r2s<NT>(sv, vt(0), P192, tid);
@@ -365,8 +368,8 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_kernel(const bf16_t* __restr
     for (int j = 0; j < nkv; j++) {
       const int cur = j & 1;
       if (j + 1 < nkv) {
-        tile_g2r<NT>(sk, Kb, (j + 1) * KT, S, tid);
-        tile_g2r<NT>(sv, Vb, (j + 1) * KT, S, tid);
+        tile_g2r<NT>(sk, Kb, (j + 1) * KT, Skv, tid);
+        tile_g2r<NT>(sv, Vb, (j + 1) * KT, Skv, tid);
       }
       f32x16 s[2];
       if (active) scores(j, kt(cur), s);
@@ -480,11 +483,12 @@ __device__ __forceinline__ bf16x8 tr_frag_sw(const char* tile, int rb, int h8, i
 // MXO (fp8 inference): the output leaves as MX e4m3 -- codes in place of the bf16 rows (same (B, tokens, H * 64) geometry, one byte per
 // feature) plus E8M0 block scales in the GEMM's layout (mx_scale_index; a head's 64 features are two 32-blocks) -- so the out-projection
 // GEMM needs no quantise pass; bit-identical to the bf16 output followed by mmdit_mxfp8_quantize.
-template <int DBG = 0, bool MXO = false, int NW = 8, int NS = ANS>
+template <int DBG = 0, bool MXO = false, int NW = 8, int NS = ANS, bool KVL = false>
 __global__ __launch_bounds__(64 * NW) void attn_fwd_dma_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
                                                            int BH, int H, int S, int n_img, float scale,
                                                            bf16_t* __restrict__ Ox, bf16_t* __restrict__ Oc, float* __restrict__ lse,
-                                                           unsigned char* __restrict__ scx = nullptr, unsigned char* __restrict__ scc = nullptr) {
+                                                           unsigned char* __restrict__ scx = nullptr, unsigned char* __restrict__ scc = nullptr, int s_kv = 0) {
+  const int Skv = KVL ? s_kv : S;      // key rows (see attn_fwd_kernel)
   constexpr int PPW = 8 / NW;   // 1 KiB pieces (8 key rows) of each operand tile this wave copies
   static_assert(NW * PPW == 8 && NS >= 2 && NW * 4096 <= NS * 2 * KT * 128, "tile pieces / epilogue staging");
   __shared__ __attribute__((aligned(16))) char smem[NS * 2 * KT * 128];
@@ -496,14 +500,14 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_dma_kernel(const bf16_t* __r
   const int h = bh % H;
   const int64_t b = bh / H;
   const bf16_t* Qb = Q + (int64_t)bh * S * HD;
-  const bf16_t* Kb = K + (int64_t)bh * S * HD;
-  const bf16_t* Vb = V + (int64_t)bh * S * HD;
+  const bf16_t* Kb = K + (int64_t)bh * Skv * HD;
+  const bf16_t* Vb = V + (int64_t)bh * Skv * HD;
   const int q = qtile * 32 * NW + wave * 32 + (lane & 31);
   const int qc = min(q, S - 1);
   const bool active = qtile * 32 * NW + wave * 32 < S;
 
   if (DBG & 64) return;   // launch floor
-  const int nkv = (S + KT - 1) / KT;
+  const int nkv = (Skv + KT - 1) / KT;
   // this lane's part of a tile: piece p = PPW * wave + i holds key rows 8 p .. 8 p + 7; row 8 p + (lane >> 3), 16-byte slot lane & 7
   const int slot = lane & 7;
   auto issue = [&](int j, int stage) {
@@ -511,7 +515,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_dma_kernel(const bf16_t* __r
     for (int i = 0; i < PPW; i++) {
       const int pc = wave * PPW + i, rl = 8 * pc + (lane >> 3);
       const int kcol = (slot ^ ((rl >> 1) & 7)) * 8, vcol = (slot ^ (4 * ((rl >> 1) & 1))) * 8;
-      const int row = min(j * KT + rl, S - 1);
+      const int row = min(j * KT + rl, Skv - 1);
       attn_glds16(Kb + (int64_t)row * HD + kcol, lds0 + stage * (2 * KT * 128) + pc * 1024);
       attn_glds16(Vb + (int64_t)row * HD + vcol, lds0 + stage * (2 * KT * 128) + KT * 128 + pc * 1024);
     }
@@ -579,10 +583,10 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_dma_kernel(const bf16_t* __r
         for (int ks = 0; ks < 4; ks++)
           s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16((DBG & 8) ? qf[(ks + 1) & 3] : *LDS_PTR(const bf16x8, kp[ks] + kb * 32 * 128), qf[ks], ks == 0 ? zero16 : s[kb], 0, 0, 0);
       }
-      if ((j + 1) * KT > S) {
+      if ((j + 1) * KT > Skv) {
 #pragma unroll
         for (int r = 0; r < 16; r++)
-          if (j * KT + kb * 32 + acc_row(r, lane) >= S) s[kb][r] = -INFINITY;
+          if (j * KT + kb * 32 + acc_row(r, lane) >= Skv) s[kb][r] = -INFINITY;
       }
     }
     float mx = -INFINITY;
@@ -636,7 +640,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_dma_kernel(const bf16_t* __r
 #endif
 #pragma unroll
     for (int kb = 0; kb < 2; kb++)
-      if (j * KT + kb * 32 < S)
+      if (j * KT + kb * 32 < Skv)
 #pragma unroll
         for (int h8 = 0; h8 < 2; h8++) {
           const bf16x8 pf = pack_frag(s[kb], h8);
@@ -713,12 +717,14 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_dma_kernel(const bf16_t* __r
 #ifndef MMDIT_DQ_WAVES
 #define MMDIT_DQ_WAVES 4
 #endif
-template <int NW, typename TG, bool FUSE = false>
+template <int NW, typename TG, bool FUSE = false, bool KVL = false>
 __global__ __launch_bounds__(NW * 64, NW == 8 ? MMDIT_DQ_WAVES : 1) void attn_bwd_dq_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
                                                                const bf16_t* __restrict__ Ox, const bf16_t* __restrict__ Oc,
                                                                const bf16_t* __restrict__ dOx, const bf16_t* __restrict__ dOc,
                                                                const float* __restrict__ lse, float* __restrict__ delta,
-                                                               int BH, int H, int S, int n_img, float scale, TG* __restrict__ dQ, QkFuse F = QkFuse()) {
+                                                               int BH, int H, int S, int n_img, float scale, TG* __restrict__ dQ, QkFuse F = QkFuse(), int s_kv = 0) {
+  static_assert(!(FUSE && KVL), "the fused QK epilogue keeps one sequence length");
+  const int Skv = KVL ? s_kv : S;      // key rows (see attn_fwd_kernel)
   // delta[q] = sum_d dO[q,d] O[q,d] is formed here from the query's own dO / O rows (each lane holds half of the 64 features of its
   // query) and written out for the dK/dV kernel that follows on the same stream -- no separate preparation pass.
   constexpr int NT = NW * 64;
@@ -742,8 +748,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? MMDIT_DQ_WAVES : 1) void attn_bw
   const int h = bh % H;
   const int64_t b = bh / H;
   const bf16_t* Qb = Q + (int64_t)bh * S * HD;
-  const bf16_t* Kb = K + (int64_t)bh * S * HD;
-  const bf16_t* Vb = V + (int64_t)bh * S * HD;
+  const bf16_t* Kb = K + (int64_t)bh * Skv * HD;
+  const bf16_t* Vb = V + (int64_t)bh * Skv * HD;
   const int q = qtile * 32 * NW + wave * 32 + (lane & 31);
   const int qc = min(q, S - 1);
   const bool active = qtile * 32 * NW + wave * 32 < S;
@@ -779,14 +785,14 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? MMDIT_DQ_WAVES : 1) void attn_bw
 #pragma unroll
     for (int r = 0; r < 16; r++) acc[db][r] = 0.f;
 
-  const int nkv = (S + KT - 1) / KT;
+  const int nkv = (Skv + KT - 1) / KT;
   u32x4 sk[DMA ? 1 : tile_chunks<NT>()], sv[DMA ? 1 : tile_chunks<NT>()];
   // DMA: this lane's 16 bytes of a tile -- key row 8 * wave + (lane >> 3), LDS slot lane & 7 holds chunk slot ^ sw2(row) (the layout
   // tile_r2s_sw writes and row_frag_d / tr_frag_d read); rows past the end re-read the last key (masked below in the ragged tile)
   const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(char, smem);
   const int rl = 8 * wave + (lane >> 3), dcol = ((lane & 7) ^ sw2(rl)) * 8;
   auto issue = [&](int j, int stage) {     // wave-uniform bases (SGPR pairs) + one 32-bit lane offset: the kernel sits at its 128-VGPR cap
-    const uint32_t voff = (uint32_t)min(min(j, nkv - 1) * KT + rl, S - 1) * (HD * 2) + dcol * 2;
+    const uint32_t voff = (uint32_t)min(min(j, nkv - 1) * KT + rl, Skv - 1) * (HD * 2) + dcol * 2;
     attn_glds16s(voff, (const char*)Kb, lds0 + stage * (2 * KT * 128) + wave * 1024);
     attn_glds16s(voff, (const char*)Vb, lds0 + stage * (2 * KT * 128) + KT * 128 + wave * 1024);
   };
@@ -805,8 +811,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? MMDIT_DQ_WAVES : 1) void attn_bw
       vtile = ktile + KT * 128;
       stage = stage + 1 == DQ_ST ? 0 : stage + 1;
     } else {
-      tile_g2r<NT>(sk, Kb, j * KT, S, tid);
-      tile_g2r<NT>(sv, Vb, j * KT, S, tid);
+      tile_g2r<NT>(sk, Kb, j * KT, Skv, tid);
+      tile_g2r<NT>(sv, Vb, j * KT, Skv, tid);
       __syncthreads();
       tile_r2s_sw<NT>(sk, ktile, tid);
       tile_r2s_sw<NT>(sv, vtile, tid);
@@ -815,7 +821,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? MMDIT_DQ_WAVES : 1) void attn_bw
     if (!active) continue;
 #pragma unroll
     for (int kb = 0; kb < 2; kb++) {
-      if (j * KT + kb * 32 >= S) continue;   // (wave-uniform) 32 padding keys contribute nothing
+      if (j * KT + kb * 32 >= Skv) continue;   // (wave-uniform) 32 padding keys contribute nothing
       f32x16 s, dp;
 #pragma unroll
       for (int r = 0; r < 16; r++) { s[r] = 0.f; dp[r] = 0.f; }
@@ -828,7 +834,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? MMDIT_DQ_WAVES : 1) void attn_bw
       // 128-VGPR cap), and the second half's VALU work issues behind the first half's MFMAs.
       // Padding keys exist in the last K/V tile only: a wave-uniform branch.  (Written as a per-element `ragged && ...` select the
       // compiler evaluated index, compare and two selects for EVERY score of EVERY tile: 4 of the loop's ~11 VALU slots per score.)
-      const bool ragged = (j + 1) * KT > S;
+      const bool ragged = (j + 1) * KT > Skv;
 #pragma unroll
       for (int h8 = 0; h8 < 2; h8++) {
         __builtin_amdgcn_sched_barrier(0);
@@ -842,7 +848,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? MMDIT_DQ_WAVES : 1) void attn_bw
         if (ragged) {
 #pragma unroll
           for (int i = 0; i < 8; i++)
-            if (j * KT + kb * 32 + acc_row(8 * h8 + i, lane) >= S) d8[8 * h8 + i] = 0.f;
+            if (j * KT + kb * 32 + acc_row(8 * h8 + i, lane) >= Skv) d8[8 * h8 + i] = 0.f;
         }
         const bf16x8 dsf = pack_frag(d8, h8);
 #pragma unroll
@@ -888,12 +894,14 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? MMDIT_DQ_WAVES : 1) void attn_bw
 // ------------------------------------------------------------------------------------------------
 // TRACE (probes build, tools/probes/attn_bwd_trace.py): lane 0 of every wave of the first 2048 workgroups records the cycle counter at
 // the phase boundaries (72 slots per wave)
-template <int NW, typename TG, bool FUSE = false, bool TRACE = false>
+template <int NW, typename TG, bool FUSE = false, bool TRACE = false, bool KVL = false>
 __global__ __launch_bounds__(NW * 64) void attn_bwd_dkv_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
                                                            const bf16_t* __restrict__ dOx, const bf16_t* __restrict__ dOc,
                                                            const float* __restrict__ lse, const float* __restrict__ delta,
                                                            int BH, int H, int S, int n_img, float scale, TG* __restrict__ dK, TG* __restrict__ dV, QkFuse F = QkFuse(),
-                                                           unsigned long long* __restrict__ trace = nullptr) {
+                                                           unsigned long long* __restrict__ trace = nullptr, int s_kv = 0) {
+  static_assert(!(FUSE && KVL), "the fused QK epilogue keeps one sequence length");
+  const int Skv = KVL ? s_kv : S;      // key rows: the grid, the stationary fragments and the outputs of this kernel (see attn_fwd_kernel)
   int tpos = 0;
   auto stamp = [&]() {
     if constexpr (TRACE) {
@@ -913,15 +921,15 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dkv_kernel(const bf16_t* __r
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   MMDIT_YOUNG_HALF_PRIO();
   int ktile, bh;
-  map_block((S + 32 * NW - 1) / (32 * NW), BH, ktile, bh);
+  map_block((Skv + 32 * NW - 1) / (32 * NW), BH, ktile, bh);
   const int h = bh % H;
   const int64_t b = bh / H;
   const bf16_t* Qb = Q + (int64_t)bh * S * HD;
-  const bf16_t* Kb = K + (int64_t)bh * S * HD;
-  const bf16_t* Vb = V + (int64_t)bh * S * HD;
+  const bf16_t* Kb = K + (int64_t)bh * Skv * HD;
+  const bf16_t* Vb = V + (int64_t)bh * Skv * HD;
   const int key = ktile * 32 * NW + wave * 32 + (lane & 31);
-  const bool active = ktile * 32 * NW + wave * 32 < S;   // wave-uniform: a wave whose 32 keys are all padding only helps with the tile copies
-  const int keyc = min(key, S - 1);
+  const bool active = ktile * 32 * NW + wave * 32 < Skv;   // wave-uniform: a wave whose 32 keys are all padding only helps with the tile copies
+  const int keyc = min(key, Skv - 1);
   const int n_txt = S - n_img, D = H * HD;
 
   bf16x8 kf[4], vf[4];
@@ -993,8 +1001,8 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dkv_kernel(const bf16_t* __r
           ds[r] = p * (dp[r] - d4[e]);
         }
       }
-      // No per-score masks in the steady state: a lane whose key is padding (key >= S) works on the clamped last key and its dK / dV
-      // column is never stored; padding QUERIES exist in the last Q / dO tile only (their rows are zero-filled, lse = delta = 0, so
+      // No per-score masks in the steady state: a lane whose key is padding (key >= Skv: the key count, S unless KVL) works on the clamped last key and its dK / dV
+      // column is never stored; padding QUERIES (>= S, the query count) exist in the last Q / dO tile only (their rows are zero-filled, lse = delta = 0, so
       // they would contribute exact zeros anyway; masked in a wave-uniform branch to keep P and dS themselves zero there).
       if ((jq + 1) * KT > S) {
 #pragma unroll
@@ -1046,9 +1054,9 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dkv_kernel(const bf16_t* __r
     }
     __syncthreads();
     if (tid < 128 && sdw[tid] != 0.f) atomicAdd(F.dw + (tid >> 6) * 128 + 64 + (tid & 63), sdw[tid]);   // [. | wk_x | . | wk_c]
-  } else if (key < S) {
-    TG* pk = dK + ((int64_t)bh * S + key) * HD;
-    TG* pv = dV + ((int64_t)bh * S + key) * HD;
+  } else if (key < Skv) {
+    TG* pk = dK + ((int64_t)bh * Skv + key) * HD;
+    TG* pv = dV + ((int64_t)bh * Skv + key) * HD;
 #pragma unroll
     for (int db = 0; db < 2; db++)
 #pragma unroll
@@ -1812,5 +1820,48 @@ extern "C" int mmdit_attn_bwd(const void* Q, const void* K, const void* V, const
   } else return MMDIT_ERR_DTYPE;
 #undef MMDIT_DQ
 #undef MMDIT_DKV
+  return mmdit_launch_status();
+}
+
+// Joint attention whose keys and values have a length of their own (Attention.py:243-251, kv_merge_attn: adjacent keys / values of each stream
+// averaged, S queries against s_kv = S / 2 keys).  Same kernels as above with the KVL flag: every key-side bound is s_kv, every query-side one
+// S; with s_kv == S the results are those of mmdit_attn_fwd / mmdit_attn_bwd bit for bit (same arithmetic in the same order).
+extern "C" int mmdit_attn_fwd_kv(const void* Q, const void* K, const void* V, int batch, int heads, int S, int s_kv, int n_img, float scale, int mode,
+                                 void* Ox, void* Oc, float* lse, mmdit_stream_t stream) {
+  MMDIT_CHECK_ARG(Q && K && V && Ox && lse && batch > 0 && heads > 0 && S > 0 && n_img > 0 && n_img <= S);
+  MMDIT_CHECK_ARG(Oc || n_img == S);
+  MMDIT_CHECK_ARG(mode == 0 || mode == 1);
+  if (s_kv < 1 || s_kv > S) return MMDIT_ERR_SHAPE;
+  hipStream_t s = (hipStream_t)stream;
+  if (mode == 1)
+    hipLaunchKernelGGL((attn_fwd_kernel<2, true, true>), dim3(((S + 63) / 64) * batch * heads), dim3(128), 0, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)V,
+                       batch * heads, heads, S, n_img, scale, (bf16_t*)Ox, (bf16_t*)Oc, lse, s_kv);
+  else
+    hipLaunchKernelGGL((attn_fwd_dma_kernel<0, false, 8, ANS, true>), dim3(((S + 255) / 256) * batch * heads), dim3(512), 0, s, (const bf16_t*)Q, (const bf16_t*)K,
+                       (const bf16_t*)V, batch * heads, heads, S, n_img, scale, (bf16_t*)Ox, (bf16_t*)Oc, lse, (unsigned char*)nullptr, (unsigned char*)nullptr, s_kv);
+  return mmdit_launch_status();
+}
+
+extern "C" int mmdit_attn_bwd_kv(const void* Q, const void* K, const void* V, const void* Ox, const void* Oc, const void* dOx, const void* dOc,
+                                 const float* lse, float* delta, int batch, int heads, int S, int s_kv, int n_img, float scale,
+                                 void* dQ, void* dK, void* dV, int dq_dtype, mmdit_stream_t stream) {
+  MMDIT_CHECK_ARG(Q && K && V && Ox && dOx && lse && delta && dQ && dK && dV && batch > 0 && heads > 0 && S > 0 && n_img > 0 && n_img <= S);
+  MMDIT_CHECK_ARG(Oc || n_img == S);
+  if (s_kv < 1 || s_kv > S) return MMDIT_ERR_SHAPE;
+  if (dq_dtype != MMDIT_BF16 && dq_dtype != MMDIT_F32) return MMDIT_ERR_DTYPE;
+  hipStream_t s = (hipStream_t)stream;
+  // the dQ grid covers the S queries (and writes delta), the dK/dV grid the s_kv keys
+#define MMDIT_BWD_KV(NW, TG)                                                                                                                                             \
+  do {                                                                                                                                                                   \
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<NW, TG, false, true>), dim3(((S + 32 * NW - 1) / (32 * NW)) * batch * heads), dim3(NW * 64), 0, s, (const bf16_t*)Q,          \
+                       (const bf16_t*)K, (const bf16_t*)V, (const bf16_t*)Ox, (const bf16_t*)Oc, (const bf16_t*)dOx, (const bf16_t*)dOc, lse, delta, batch * heads, heads, \
+                       S, n_img, scale, (TG*)dQ, QkFuse(), s_kv);                                                                                                        \
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<NW, TG, false, false, true>), dim3(((s_kv + 32 * NW - 1) / (32 * NW)) * batch * heads), dim3(NW * 64), 0, s,                 \
+                       (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)V, (const bf16_t*)dOx, (const bf16_t*)dOc, lse, delta, batch * heads, heads, S, n_img, scale,   \
+                       (TG*)dK, (TG*)dV, QkFuse(), (unsigned long long*)nullptr, s_kv);                                                                                  \
+  } while (0)
+  if (dq_dtype == MMDIT_BF16) MMDIT_BWD_KV(8, bf16_t);
+  else MMDIT_BWD_KV(2, float);
+#undef MMDIT_BWD_KV
   return mmdit_launch_status();
 }

@@ -610,6 +610,158 @@ __global__ __launch_bounds__(1024) void qk_norm_rope_bwd_pair_kernel(QkProb p0, 
 }
 
 // -------------------------------------------------------------------------------------------
+// kv_merge_attn (Attention.py:243-251): the same norm / RoPE / head split, but the keys and values of adjacent token PAIRS (2 j, 2 j + 1 of
+// one stream, flattened token order) leave as their mean: K' / V' have s_total / 2 rows, pair j of a stream at row tok0 / 2 + j.  A workgroup
+// of 24 * heads threads (thread = (part, head, 8-element chunk), as above) owns BOTH qkv rows of a pair: each key is normalised and rotated
+// with its own token's factors in fp32, the two fp32 results are averaged and rounded to bf16 ONCE; V is the mean of the two raw rows
+// (halving is exact: the bf16 sum halved, as the reference's autocast computes it, is the same number); Q is written per token with the
+// arithmetic of qk_norm_rope_fwd_body.  Backward: dK' / dV' of a pair are read once, halved and pushed through each token's own RoPE / norm
+// backward; the norm-weight gradients accumulate as in qk_norm_rope_bwd_body.
+// -------------------------------------------------------------------------------------------
+template <typename TI>
+__device__ __forceinline__ void qk_merge_fwd_body(int bid, int pstride, const TI* __restrict__ qkv, const float* __restrict__ wq, const float* __restrict__ wk,
+                                                  const float* __restrict__ rcos, const float* __restrict__ rsin,
+                                                  int pairs, int tokens, int heads, int s_total, int tok0,
+                                                  bf16_t* __restrict__ Q, bf16_t* __restrict__ K, bf16_t* __restrict__ V) {
+  const int hc = threadIdx.x % (8 * heads), part = threadIdx.x / (8 * heads), head = hc >> 3, chunk = hc & 7;
+  const int tp = tokens >> 1, s_kv = s_total >> 1, kv0 = tok0 >> 1;      // pairs per sample, rows of K' / V', first merged row of this stream
+  float w[8];
+#pragma unroll
+  for (int e = 0; e < 8; e++) w[e] = 0.f;
+  if (part < 2) ld8((part == 0 ? wq : wk) + chunk * 8, w);
+  for (int pr = bid; pr < pairs; pr += pstride) {
+    const int b = pr / tp, j = pr - b * tp;
+    float x[2][8], cs[2][8], sn[2][8];
+#pragma unroll
+    for (int k = 0; k < 2; k++) ld8(qkv + ((((int64_t)pr * 2 + k) * 3 + part) * heads + head) * 64 + chunk * 8, x[k]);
+    if (part < 2 && rcos) {
+#pragma unroll
+      for (int k = 0; k < 2; k++) {
+        ld8(rcos + (int64_t)(2 * j + k) * 64 + chunk * 8, cs[k]);
+        ld8(rsin + (int64_t)(2 * j + k) * 64 + chunk * 8, sn[k]);
+      }
+    }
+    if (part < 2) {
+#pragma unroll
+      for (int k = 0; k < 2; k++) {
+        float ss = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; e++) ss += x[k][e] * x[k][e];
+        const float rinv = rsqrtf(group8_sum(ss) * (1.f / 64.f) + RMS_EPS);
+#pragma unroll
+        for (int e = 0; e < 8; e++) x[k][e] = x[k][e] * rinv * w[e];
+        if (rcos) {
+#pragma unroll
+          for (int p = 0; p < 4; p++) {
+            float a = x[k][2 * p], bb = x[k][2 * p + 1];
+            x[k][2 * p] = a * cs[k][2 * p] - bb * sn[k][2 * p];
+            x[k][2 * p + 1] = bb * cs[k][2 * p + 1] + a * sn[k][2 * p + 1];
+          }
+        }
+      }
+    }
+    if (part == 0) {
+#pragma unroll
+      for (int k = 0; k < 2; k++) st8(Q + (((int64_t)b * heads + head) * s_total + tok0 + 2 * j + k) * 64 + chunk * 8, x[k]);
+    } else {
+      float m[8];
+#pragma unroll
+      for (int e = 0; e < 8; e++) m[e] = (x[0][e] + x[1][e]) * 0.5f;
+      st8((part == 1 ? K : V) + (((int64_t)b * heads + head) * s_kv + kv0 + j) * 64 + chunk * 8, m);
+    }
+  }
+}
+template <typename TI>
+__global__ __launch_bounds__(512) void qk_merge_fwd_pair_kernel(QkProb p0, QkProb p1, int g0, int heads, int s_total,
+                                                                 bf16_t* __restrict__ Q, bf16_t* __restrict__ K, bf16_t* __restrict__ V) {
+  const bool first = (int)blockIdx.x < g0;     // (workgroup-uniform)
+  const QkProb& p = first ? p0 : p1;
+  qk_merge_fwd_body<TI>(first ? (int)blockIdx.x : (int)blockIdx.x - g0, first ? g0 : (int)gridDim.x - g0, (const TI*)p.qkv, p.wq, p.wk, p.rcos, p.rsin,
+                        p.rows >> 1, p.tokens, heads, s_total, p.tok0, Q, K, V);
+}
+
+template <typename TG, typename TI, typename TO>
+__device__ __forceinline__ void qk_merge_bwd_body(int bid, int pstride, const TG* __restrict__ dQ, const TG* __restrict__ dK, const TG* __restrict__ dV,
+                                                  const TI* __restrict__ qkv, const float* __restrict__ wq, const float* __restrict__ wk,
+                                                  const float* __restrict__ rcos, const float* __restrict__ rsin,
+                                                  int pairs, int tokens, int heads, int s_total, int tok0,
+                                                  TO* __restrict__ dqkv, float* __restrict__ dwq, float* __restrict__ dwk) {
+  __shared__ float sdw[2][64];
+  for (int i = threadIdx.x; i < 128; i += blockDim.x) sdw[i >> 6][i & 63] = 0.f;
+  __syncthreads();
+  const int hc = threadIdx.x % (8 * heads), part = threadIdx.x / (8 * heads), head = hc >> 3, chunk = hc & 7;
+  const int tp = tokens >> 1, s_kv = s_total >> 1, kv0 = tok0 >> 1;
+  float w[8], aw[8];
+#pragma unroll
+  for (int e = 0; e < 8; e++) { w[e] = 0.f; aw[e] = 0.f; }
+  if (part < 2) ld8((part == 0 ? wq : wk) + chunk * 8, w);
+  for (int pr = bid; pr < pairs; pr += pstride) {
+    const int b = pr / tp, j = pr - b * tp;
+    float dz[2][8], x[2][8], cs[2][8], sn[2][8];
+    if (part == 0) {
+#pragma unroll
+      for (int k = 0; k < 2; k++) ld8_nt(dQ + (((int64_t)b * heads + head) * s_total + tok0 + 2 * j + k) * 64 + chunk * 8, dz[k]);
+    } else {      // one read of the merged row's gradient, half of it for each token of the pair
+      ld8_nt((part == 1 ? dK : dV) + (((int64_t)b * heads + head) * s_kv + kv0 + j) * 64 + chunk * 8, dz[0]);
+#pragma unroll
+      for (int e = 0; e < 8; e++) { dz[0][e] *= 0.5f; dz[1][e] = dz[0][e]; }
+    }
+    if (part < 2) {
+#pragma unroll
+      for (int k = 0; k < 2; k++) {
+        ld8_nt(qkv + ((((int64_t)pr * 2 + k) * 3 + part) * heads + head) * 64 + chunk * 8, x[k]);
+        if (rcos) {
+          ld8(rcos + (int64_t)(2 * j + k) * 64 + chunk * 8, cs[k]);
+          ld8(rsin + (int64_t)(2 * j + k) * 64 + chunk * 8, sn[k]);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 2; k++) {
+        float ss = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; e++) ss += x[k][e] * x[k][e];
+        const float rinv = rsqrtf(group8_sum(ss) * (1.f / 64.f) + RMS_EPS);
+        if (rcos) {      // transpose of the rotation
+#pragma unroll
+          for (int p = 0; p < 4; p++) {
+            float da = dz[k][2 * p], db = dz[k][2 * p + 1];
+            dz[k][2 * p] = da * cs[k][2 * p] + db * sn[k][2 * p + 1];
+            dz[k][2 * p + 1] = db * cs[k][2 * p + 1] - da * sn[k][2 * p];
+          }
+        }
+        float dot = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+          float xh = x[k][e] * rinv;
+          aw[e] += dz[k][e] * xh;
+          dz[k][e] *= w[e];                 // d(xhat)
+          dot += dz[k][e] * xh;
+          x[k][e] = xh;
+        }
+        dot = group8_sum(dot) * (1.f / 64.f);
+#pragma unroll
+        for (int e = 0; e < 8; e++) dz[k][e] = rinv * (dz[k][e] - x[k][e] * dot);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 2; k++) st8(dqkv + ((((int64_t)pr * 2 + k) * 3 + part) * heads + head) * 64 + chunk * 8, dz[k]);
+  }
+  if (part < 2) {
+#pragma unroll
+    for (int e = 0; e < 8; e++) atomicAdd(&sdw[part][chunk * 8 + e], aw[e]);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 128; i += blockDim.x) atomicAdd((i < 64 ? dwq : dwk) + (i & 63), sdw[i >> 6][i & 63]);
+}
+template <typename TG, typename TI, typename TO>
+__global__ __launch_bounds__(512) void qk_merge_bwd_pair_kernel(QkProb p0, QkProb p1, int g0, int heads, int s_total) {
+  const bool first = (int)blockIdx.x < g0;     // (workgroup-uniform)
+  const QkProb& p = first ? p0 : p1;
+  qk_merge_bwd_body<TG, TI, TO>(first ? (int)blockIdx.x : (int)blockIdx.x - g0, first ? g0 : (int)gridDim.x - g0, (const TG*)p.dQ, (const TG*)p.dK, (const TG*)p.dV,
+                                (const TI*)p.qkv, p.wq, p.wk, p.rcos, p.rsin, p.rows >> 1, p.tokens, heads, s_total, p.tok0, (TO*)p.dqkv, p.dwq, p.dwk);
+}
+
+// -------------------------------------------------------------------------------------------
 // column-owner elementwise kernels: block = 2 row-lanes x 128 column threads (8 columns each);
 // grid = (column slabs of 1024, row chunks of CO_RCH rows).
 // -------------------------------------------------------------------------------------------
@@ -1285,6 +1437,61 @@ extern "C" int mmdit_qk_norm_rope_bwd_pair(const mmdit_qk_problem* a, const mmdi
   else if (dq_dtype == MMDIT_BF16 && qkv_dtype == MMDIT_F32 && dqkv_dtype == MMDIT_F32) QKP(bf16_t, float, float);
   else return MMDIT_ERR_DTYPE;
 #undef QKP
+  return mmdit_launch_status();
+}
+
+// kv_merge_attn (Attention.py:243-251): see qk_merge_fwd_body.  K / V: (batch, heads, s_total / 2, 64); Q and dQ as in the plain pair launches.
+static int qk_merge_check(const mmdit_qk_problem* p, int s_total, bool bwd) {
+  if (!(p->qkv && p->wq && p->wk && p->tokens > 0 && p->tok0 >= 0 && p->tok0 + p->tokens <= s_total && (p->rope_cos == nullptr) == (p->rope_sin == nullptr))) return MMDIT_ERR_ARG;
+  if (bwd && !(p->dqkv && p->dwq && p->dwk)) return MMDIT_ERR_ARG;
+  if ((p->tokens | p->tok0 | s_total) & 1) return MMDIT_ERR_SHAPE;      // a pair never straddles two streams or two samples
+  return 0;
+}
+extern "C" int mmdit_qk_norm_rope_fwd_merge_pair(const mmdit_qk_problem* a, const mmdit_qk_problem* b, int qkv_dtype, int batch, int heads, int s_total,
+                                                 void* Q, void* K, void* V, mmdit_stream_t stream) {
+  MMDIT_CHECK_ARG(a && b && Q && K && V && batch > 0 && heads > 0 && 24 * heads <= 512);      // one pair per workgroup of 24 * heads threads; the kernels are bounded at 512 (255 VGPRs: both rows of a pair and their factors stay in registers)
+  if (qkv_dtype != MMDIT_BF16 && qkv_dtype != MMDIT_F32) return MMDIT_ERR_DTYPE;
+  const mmdit_qk_problem* src[2] = {a, b};
+  QkProb q[2];
+  int g[2];
+  for (int i = 0; i < 2; i++) {
+    const mmdit_qk_problem* p = src[i];
+    if (int e = qk_merge_check(p, s_total, false)) return e;
+    const int pairs = batch * (p->tokens / 2);
+    g[i] = pairs < 1024 ? pairs : 1024;
+    q[i] = QkProb{p->qkv, p->wq, p->wk, p->rope_cos, p->rope_sin, batch * p->tokens, p->tokens, p->tok0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  }
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid(g[0] + g[1]);
+  if (qkv_dtype == MMDIT_BF16) hipLaunchKernelGGL((qk_merge_fwd_pair_kernel<bf16_t>), grid, dim3(24 * heads), 0, s, q[0], q[1], g[0], heads, s_total, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V);
+  else hipLaunchKernelGGL((qk_merge_fwd_pair_kernel<float>), grid, dim3(24 * heads), 0, s, q[0], q[1], g[0], heads, s_total, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V);
+  return mmdit_launch_status();
+}
+
+extern "C" int mmdit_qk_norm_rope_bwd_merge_pair(const mmdit_qk_problem* a, const mmdit_qk_problem* b, const void* dQ, const void* dK, const void* dV, int dq_dtype,
+                                                 int qkv_dtype, int dqkv_dtype, int batch, int heads, int s_total, mmdit_stream_t stream) {
+  MMDIT_CHECK_ARG(a && b && dQ && dK && dV && batch > 0 && heads > 0 && 24 * heads <= 512);
+  const int combo = (dq_dtype == MMDIT_BF16 && qkv_dtype == MMDIT_BF16 && dqkv_dtype == MMDIT_BF16) ? 0
+                  : (dq_dtype == MMDIT_F32 && qkv_dtype == MMDIT_F32 && dqkv_dtype == MMDIT_F32)    ? 1
+                  : (dq_dtype == MMDIT_BF16 && qkv_dtype == MMDIT_F32 && dqkv_dtype == MMDIT_F32)   ? 2 : -1;
+  if (combo < 0) return MMDIT_ERR_DTYPE;
+  const mmdit_qk_problem* src[2] = {a, b};
+  QkProb q[2];
+  int g[2];
+  for (int i = 0; i < 2; i++) {
+    const mmdit_qk_problem* p = src[i];
+    if (int e = qk_merge_check(p, s_total, true)) return e;
+    const int pairs = batch * (p->tokens / 2);
+    g[i] = pairs < 512 ? pairs : 512;      // (every workgroup ends with 128 global atomics on the same two cache lines: a small grid)
+    q[i] = QkProb{p->qkv, p->wq, p->wk, p->rope_cos, p->rope_sin, batch * p->tokens, p->tokens, p->tok0, dQ, dK, dV, p->dqkv, p->dwq, p->dwk};
+  }
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid(g[0] + g[1]);
+#define QKM(TG, TI, TO) hipLaunchKernelGGL((qk_merge_bwd_pair_kernel<TG, TI, TO>), grid, dim3(24 * heads), 0, s, q[0], q[1], g[0], heads, s_total)
+  if (combo == 0) QKM(bf16_t, bf16_t, bf16_t);
+  else if (combo == 1) QKM(float, float, float);
+  else QKM(bf16_t, float, float);
+#undef QKM
   return mmdit_launch_status();
 }
 

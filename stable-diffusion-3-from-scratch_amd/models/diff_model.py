@@ -74,9 +74,10 @@ class diff_model(nn.Module):
 
         assert positional_encoding in ["absolute", "RoPE", "NoPE", "RoPE2d", "RoPE2dV2"], "positional_encoding must be 'absolute', 'RoPE', or 'NoPE' or 'RoPE2d' or 'RoPE2dV2'"
         assert MLP_type in ["gelu", "swiglu", "swiglu_old"]
-        if positional_encoding != "RoPE2d" or text_loss or kv_merge_attn or qk_half_dim or MLP_type == "swiglu_old":
+        if positional_encoding != "RoPE2d" or text_loss or qk_half_dim or MLP_type == "swiglu_old":
             raise RuntimeError("diff_model (HIP path): only the trained configuration is implemented: positional_encoding='RoPE2d', "
-                               "MLP_type in {'swiglu','gelu'}, text_loss=False, kv_merge_attn=False, qk_half_dim=False")
+                               "MLP_type in {'swiglu','gelu'}, text_loss=False, qk_half_dim=False")
+        self.kv_merge_attn = bool(kv_merge_attn)
         if patch_size != 2:
             raise RuntimeError("diff_model (HIP path): patch_size must be 2 (Attention.py:178-179 hard-codes it too)")
         self.legacy_MLP = False
@@ -153,6 +154,8 @@ class diff_model(nn.Module):
         """"fast" (bf16, training and inference), "parity" (fp32-exact GEMMs, the 1e-3 golden check) or "fp8": inference
         only -- e4m3 operands with per-tensor scales for the QKV / out / MLP GEMMs of every block (BASELINE config 5)."""
         assert precision in ("fast", "parity", "fp8", "mxfp8")
+        if precision in ("fp8", "mxfp8") and self.kv_merge_attn:
+            raise RuntimeError(f"set_precision('{precision}'): kv_merge_attn has no e4m3 path (mmdit_attn_fwd_mx keeps one sequence length); use 'fast' or 'parity'")
         engine.FP8._q.clear()
         engine.MXFP8._q.clear()
         for mod in self.modules():

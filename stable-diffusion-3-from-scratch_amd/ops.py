@@ -631,7 +631,62 @@ def qk_norm_rope_bwd_pair(dQ, dK, dV, img, txt, batch, heads, s_total, out_dtype
     return outs
 
 
-def attn_fwd(Q, K, V, n_img, scale, mode):
+def _merge_status(status, what):
+    if status == _lib.ERR_SHAPE:
+        raise RuntimeError(f"{what}: kv_merge_attn averages adjacent token pairs -- the tokens of each stream, its offset and the joint length must be even")
+    check(status, what)
+
+
+def qk_norm_rope_fwd_merge_pair(img, txt, batch, heads, s_total, Q, K, V):
+    """kv_merge_attn (Attention.py:243-251): qk_norm_rope_fwd_pair with the keys / values of adjacent token pairs averaged
+    (mmdit_qk_norm_rope_fwd_merge_pair).  img / txt = (qkv, wq, wk, rope_cos, rope_sin, tokens, tok0); Q is (batch, heads, s_total, 64),
+    K and V are (batch, heads, s_total / 2, 64), the pairs of a stream from row tok0 / 2."""
+    for t, rows in ((Q, s_total), (K, s_total // 2), (V, s_total // 2)):
+        if t.dtype != torch.bfloat16 or tuple(t.shape) != (batch, heads, rows, 64):
+            raise RuntimeError(f"qk_norm_rope_fwd_merge_pair: Q / K / V are bfloat16 (batch, heads, {s_total} | {s_total // 2}, 64), got {t.dtype} {tuple(t.shape)}")
+        _c(t)
+    probs, keep = (_lib.QkProblem * 2)(), []
+    for q, (qkv, wq, wk, rc, rs, tokens, tok0) in zip(probs, (img, txt)):
+        qkv = _c(qkv)
+        keep.append(qkv)
+        q.qkv, q.wq, q.wk, q.rope_cos, q.rope_sin, q.tokens, q.tok0 = _p(qkv), _p(wq), _p(wk), _p(rc), _p(rs), tokens, tok0
+    _merge_status(_lib.lib().mmdit_qk_norm_rope_fwd_merge_pair(ctypes.byref(probs[0]), ctypes.byref(probs[1]), _dt(img[0]), batch, heads, s_total,
+                                                                _p(Q), _p(K), _p(V), _s()), "mmdit_qk_norm_rope_fwd_merge_pair")
+
+
+def qk_norm_rope_bwd_merge_pair(dQ, dK, dV, img, txt, batch, heads, s_total, out_dtype):
+    """Backward of qk_norm_rope_fwd_merge_pair (mmdit_qk_norm_rope_bwd_merge_pair): dQ (batch, heads, s_total, 64), dK / dV (batch, heads,
+    s_total / 2, 64).  img / txt = (qkv, wq, wk, rope_cos, rope_sin, tokens, tok0, dwq, dwk); returns (dqkv_img, dqkv_txt), ADDS to dwq / dwk."""
+    for t, rows in ((dQ, s_total), (dK, s_total // 2), (dV, s_total // 2)):
+        if t.dtype != dQ.dtype or tuple(t.shape) != (batch, heads, rows, 64):
+            raise RuntimeError(f"qk_norm_rope_bwd_merge_pair: dQ / dK / dV are (batch, heads, {s_total} | {s_total // 2}, 64) of one dtype, got {t.dtype} {tuple(t.shape)}")
+        _c(t)
+    probs, outs = (_lib.QkProblem * 2)(), []
+    for q, (qkv, wq, wk, rc, rs, tokens, tok0, dwq, dwk) in zip(probs, (img, txt)):
+        dqkv = torch.empty(qkv.shape, dtype=out_dtype, device=qkv.device)
+        q.qkv, q.wq, q.wk, q.rope_cos, q.rope_sin, q.tokens, q.tok0 = _p(_c(qkv)), _p(wq), _p(wk), _p(rc), _p(rs), tokens, tok0
+        q.dqkv, q.dwq, q.dwk = _p(dqkv), _p(dwq), _p(dwk)
+        outs.append(dqkv)
+    _merge_status(_lib.lib().mmdit_qk_norm_rope_bwd_merge_pair(ctypes.byref(probs[0]), ctypes.byref(probs[1]), _p(dQ), _p(dK), _p(dV), _dt(dQ), _dt(img[0]),
+                                                                _DT[out_dtype], batch, heads, s_total, _s()), "mmdit_qk_norm_rope_bwd_merge_pair")
+    return outs
+
+
+def _kv_operands(Q, K, V, s_kv):
+    """Checks of the launches whose K / V have s_kv rows of their own (mmdit_attn_fwd_kv / mmdit_attn_bwd_kv)."""
+    batch, heads, S, hd = Q.shape
+    if hd != 64:
+        raise RuntimeError("attention kernels are built for head_dim 64 (the reference's dim = 64*num_heads convention)")
+    if tuple(K.shape) != (batch, heads, s_kv, hd) or K.shape != V.shape:
+        raise RuntimeError(f"attention with s_kv={s_kv}: K and V must be (batch, heads, s_kv, 64) = {(batch, heads, s_kv, hd)}, got {tuple(K.shape)} / {tuple(V.shape)}")
+    for t in (Q, K, V):
+        if t.dtype != torch.bfloat16:
+            raise RuntimeError("attention operands are bfloat16")
+        _c(t)
+
+
+def attn_fwd(Q, K, V, n_img, scale, mode, s_kv=None):
+    """s_kv (kv_merge_attn, Attention.py:243-251): K and V are (batch, heads, s_kv, 64), 1 <= s_kv <= S; None = the plain launch."""
     batch, heads, S, hd = Q.shape
     if hd != 64:
         raise RuntimeError("attention kernels are built for head_dim 64 (the reference's dim = 64*num_heads convention)")
@@ -639,14 +694,25 @@ def attn_fwd(Q, K, V, n_img, scale, mode):
     Ox = torch.empty((batch, n_img, D), dtype=torch.bfloat16, device=Q.device)
     Oc = torch.empty((batch, S - n_img, D), dtype=torch.bfloat16, device=Q.device) if S > n_img else None
     lse = torch.empty((batch, heads, S), dtype=torch.float32, device=Q.device)
+    if s_kv is not None:
+        _kv_operands(Q, K, V, s_kv)
+        check(_lib.lib().mmdit_attn_fwd_kv(_p(Q), _p(K), _p(V), batch, heads, S, int(s_kv), n_img, float(scale), mode, _p(Ox), _p(Oc), _p(lse), _s()), "mmdit_attn_fwd_kv")
+        return Ox, Oc, lse
     check(_lib.lib().mmdit_attn_fwd(_p(Q), _p(K), _p(V), batch, heads, S, n_img, float(scale), mode, _p(Ox), _p(Oc), _p(lse), _s()), "mmdit_attn_fwd")
     return Ox, Oc, lse
 
 
-def attn_bwd(Q, K, V, Ox, Oc, dOx, dOc, lse, n_img, scale, out_dtype):
+def attn_bwd(Q, K, V, Ox, Oc, dOx, dOc, lse, n_img, scale, out_dtype, s_kv=None):
     batch, heads, S, hd = Q.shape
     delta = torch.empty((batch, heads, S), dtype=torch.float32, device=Q.device)
     dQ = torch.empty(Q.shape, dtype=out_dtype, device=Q.device)
+    if s_kv is not None:      # dK / dV follow K / V: (batch, heads, s_kv, 64)
+        _kv_operands(Q, K, V, s_kv)
+        dK = torch.empty(K.shape, dtype=out_dtype, device=Q.device)
+        dV = torch.empty(K.shape, dtype=out_dtype, device=Q.device)
+        check(_lib.lib().mmdit_attn_bwd_kv(_p(Q), _p(K), _p(V), _p(_c(Ox)), _p(_c(Oc)), _p(_c(dOx)), _p(_c(dOc)), _p(_c(lse)), _p(delta), batch, heads, S, int(s_kv),
+                                           n_img, float(scale), _p(dQ), _p(dK), _p(dV), _dt(dQ), _s()), "mmdit_attn_bwd_kv")
+        return dQ, dK, dV
     dK = torch.empty(Q.shape, dtype=out_dtype, device=Q.device)
     dV = torch.empty(Q.shape, dtype=out_dtype, device=Q.device)
     check(_lib.lib().mmdit_attn_bwd(_p(Q), _p(K), _p(V), _p(Ox), _p(Oc), _p(_c(dOx)), _p(_c(dOc)), _p(lse), _p(delta), batch, heads, S, n_img,
