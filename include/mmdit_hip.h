@@ -46,7 +46,7 @@ extern "C" {
 #define MMDIT_ACT_SWIGLU_BWD 3  /* data gradient of the SwiGLU down-projection fused with the activation backward (MLP.py:32 backward / xformers
                                  * SwiGLU w3, then silu(g) * u): A = dY [M, K] row-major bf16, B = w3 [K, N] (b_kmajor = 1, N = h), aux [M, 2h] (bf16,
                                  * INPUT) = the [g | u] kept by MMDIT_ACT_SWIGLU, C [M, 2h] (bf16, ldc >= 2h) = d[g | u] computed from the
-                                 * bf16-rounded dh = A B (== mmdit_gemm followed by mmdit_swiglu_bwd, bit for bit, without the dh round trip);
+                                 * bf16-rounded dh = A B (== mmdit_gemm followed by mmdit_mlp_act_bwd, bit for bit, without the dh round trip);
                                  * dbias (optional, fp32 [2h], PRE-ZEROED or accumulating) += column sums of d[g | u].  h % 8 == 0, K % 64 == 0;
                                  * MMDIT_ERR_SHAPE when the planner would not give the launch to the 8-phase 256 x 256 kernel (run the two
                                  * passes instead); no bias / gate / residual / split. */
@@ -61,7 +61,7 @@ typedef void* mmdit_stream_t;   /* hipStream_t */
  * (MMDIT_LIB=...) with another layout fails loudly instead of reading past a struct.  mmdit_struct_size(which): sizeof of
  * 0 mmdit_gemm_args, 1 mmdit_ln_fwd_problem, 2 mmdit_ln_bwd_problem, 3 mmdit_qk_problem, 4 mmdit_mlp_bwd_problem,
  * 5 mmdit_adamw_tensor, 6 mmdit_cast_tensor, 7 mmdit_qk_epilogue; -1 for an unknown id. */
-#define MMDIT_ABI_VERSION 9
+#define MMDIT_ABI_VERSION 10
 int mmdit_abi_version(void);
 int mmdit_struct_size(int which);
 const char* mmdit_build_arch(void);
@@ -153,7 +153,7 @@ int mmdit_gemm_zero_mask(const mmdit_gemm_args* args, int count, unsigned* mask)
  * RMS-normalised over the 64 features of their head (weights wq / wk, eps = finfo(float32).eps) and, when rope_cos / rope_sin (tokens, 64)
  * are given, rotated -- the arithmetic of mmdit_qk_norm_rope_fwd on the ROUNDED raw values, i.e. the same results without its pass.
  * MMDIT_ERR_SHAPE when the planner would not give these problems to the lean wide-slot kernel (run mmdit_gemm_grouped +
- * mmdit_qk_norm_rope_fwd_pair instead).  args[i].C may be NULL (inference: nobody reads the raw projection): the q / k columns are then not written
+ * mmdit_qk_norm_rope_fwd instead).  args[i].C may be NULL (inference: nobody reads the raw projection): the q / k columns are then not written
  * either -- by the 8-phase kernel's epilogue only (e4m3 operands with MX scales, or bf16 operands with tile claiming on), MMDIT_ERR_SHAPE otherwise. */
 typedef struct mmdit_qk_epilogue {
   const float* wq; const float* wk;
@@ -218,8 +218,8 @@ int mmdit_mxfp8_quantize(const void* x, int x_dtype, int rows, int K, int64_t ld
 /* MX-producing variants of the three kernels whose outputs feed the fp8 GEMMs of a block (inference, "mxfp8" precision): the
  * activation leaves its producer as e4m3 codes + E8M0 block scales (layout and size as for mmdit_gemm_args.scale_mode 1), bit-identical to the bf16 output followed by mmdit_mxfp8_quantize -- no quantise pass in front of the
  * QKV / out-projection / MLP GEMMs.
- *   mmdit_ln_modulate_fwd_mx: adaLN (Norm.py:16-22), optionally with the pending gated residual update of mmdit_ln_modulate_fwd_res
- *     (acc != NULL: bf16 acc, writes x_out); d % 64 == 0.
+ *   mmdit_ln_modulate_fwd_mx: adaLN (Norm.py:16-22), optionally with the pending gated residual update of mmdit_ln_modulate_fwd
+ *     (acc != NULL: bf16 acc, writes x_out); d % 64 == 0.  A list of one on the same kernel.
  *   mmdit_swiglu_fwd_mx: SwiGLU activation of the bf16 pre-activations [g | u] (MLP.py:25-40); hidden % 64 == 0.
  *   mmdit_attn_fwd_mx: flash attention forward (mode 0 of mmdit_attn_fwd) writing Ox / Oc as e4m3 (B, tokens, heads * 64) with scales
  *     in that layout (K = heads * 64); no lse (inference). */
@@ -242,51 +242,33 @@ int mmdit_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t
  * bwd: dx = dres + LN-backward(dout * (1+scale));  dscale[b,:] += sum_rows dout*xhat;
  *      dshift[b,:] += sum_rows dout   (atomic fp32 accumulation, caller zero-inits).
  * d%4==0, d<=4096.
+ * Both entry points take a LIST of count = 1 or 2 problems of the same d and dtypes and run it in ONE launch (else MMDIT_ERR_ARG, nothing
+ * is launched).  Two problems are the image and the text stream of a block, which run the same kernel on different rows, modulation vectors
+ * and rows per sample: these 20-45 us kernels pay ~8 us of ramp-up and tail per launch.
+ * acc != NULL in EVERY problem of the list (a mixed list is MMDIT_ERR_ARG) selects the forms fused with the gated residual update of
+ * blocks/Transformer_Block_Dual.py:64-76 (gate fp32 (batch, ld_gate)):
+ *   fwd: the update that PRODUCES the norm's input: x_out = x + gate[b,:] * acc (acc = the projection GEMM's output, acc_dtype == out_dtype),
+ *        out = LayerNorm(x_out) * (1 + scale[b,:]) + shift[b,:].  The projection GEMM then needs no fp32 gate/residual epilogue;
+ *        mmdit_gate_residual_fwd is the update on its own.
+ *   bwd: the backward of the update that consumes dx next in the backward order (X_out = acc * gate[b,:] + X_in; dx = d(X_out)):
+ *        dacc = dx * gate[b,:]  (acc's dtype = dout's dtype),  dgate[b,:] += sum_rows dx * acc,
+ *        dbias[b,:] += sum_rows dacc  (optional, may be NULL: per-batch partial rows of the producing projection's bias gradient).
+ *        Replaces the plain backward followed by mmdit_gate_residual_bwd on the same rows.
  * ------------------------------------------------------------------------- */
-int mmdit_ln_modulate_fwd(const float* x, const float* scale, const float* shift, int64_t ld_mod,
-                          int rows, int d, int rows_per_batch,
-                          void* out, int out_dtype, float* mean, float* rstd, mmdit_stream_t stream);
-/* adaLN forward fused with the gated residual update that PRODUCES its input (blocks/Transformer_Block_Dual.py:64-76):
- *   x_out = x + gate[b,:] * acc   (acc = the projection GEMM's output in the activation dtype, gate fp32 (batch, ld_gate));
- *   out = LayerNorm(x_out) * (1 + scale[b,:]) + shift[b,:].
- * The projection GEMM then needs no fp32 gate/residual epilogue.  mmdit_gate_residual_fwd is the update on its own. */
-int mmdit_ln_modulate_fwd_res(const float* x, const void* acc, int acc_dtype, const float* gate, int64_t ld_gate, float* x_out,
-                              const float* scale, const float* shift, int64_t ld_mod,
-                              int rows, int d, int rows_per_batch,
-                              void* out, int out_dtype, float* mean, float* rstd, mmdit_stream_t stream);
-/* The image and the text stream of a block run the same adaLN kernels on different rows, modulation vectors and rows-per-sample: the
- * *_pair entry points take both problems (same d, same dtypes) in ONE launch -- these 20-45 us kernels pay ~8 us of ramp-up and tail
- * per launch.  Field meaning as in mmdit_ln_modulate_fwd_res / mmdit_ln_modulate_bwd_gated (acc == NULL in BOTH problems: the plain
- * mmdit_ln_modulate_fwd / _bwd arithmetic; dbias may be NULL). */
 typedef struct mmdit_ln_fwd_problem {
   const float* x; const void* acc; const float* gate; int64_t ld_gate; float* x_out;
   const float* scale; const float* shift; int64_t ld_mod; int rows, rows_per_batch;
   void* out; float* mean; float* rstd;
 } mmdit_ln_fwd_problem;
-int mmdit_ln_modulate_fwd_pair(const mmdit_ln_fwd_problem* p0, const mmdit_ln_fwd_problem* p1, int d, int acc_dtype, int out_dtype, mmdit_stream_t stream);
+int mmdit_ln_modulate_fwd(const mmdit_ln_fwd_problem* probs, int count, int d, int acc_dtype, int out_dtype, mmdit_stream_t stream);
 typedef struct mmdit_ln_bwd_problem {
   const void* dout; const float* x; const float* mean; const float* rstd; const float* scale; int64_t ld_mod; const float* dres; int rows, rows_per_batch;
   float* dx; float* dscale; float* dshift; int64_t ld_dmod;
   const void* acc; const float* gate; int64_t ld_gate; void* dacc; float* dgate; int64_t ld_dgate; float* dbias; int64_t ld_dbias;
 } mmdit_ln_bwd_problem;
-int mmdit_ln_modulate_bwd_pair(const mmdit_ln_bwd_problem* p0, const mmdit_ln_bwd_problem* p1, int d, int dout_dtype, mmdit_stream_t stream);
+int mmdit_ln_modulate_bwd(const mmdit_ln_bwd_problem* probs, int count, int d, int dout_dtype, mmdit_stream_t stream);
 int mmdit_gate_residual_fwd(const float* x, const void* acc, int acc_dtype, const float* gate, int64_t ld_gate,
                             int rows, int d, int rows_per_batch, float* out, mmdit_stream_t stream);
-int mmdit_ln_modulate_bwd(const void* dout, int dout_dtype, const float* x, const float* mean, const float* rstd,
-                          const float* scale, int64_t ld_mod, const float* dres,
-                          int rows, int d, int rows_per_batch,
-                          float* dx, float* dscale, float* dshift, int64_t ld_dmod, mmdit_stream_t stream);
-/* The same, fused with the backward of the gated residual update that consumes dx next in the backward order
- * (X_out = acc * gate[b,:] + X_in, blocks/Transformer_Block_Dual.py:64-76; dx = d(X_out)):
- *   dacc = dx * gate[b,:]  (acc's dtype = dout's dtype),  dgate[b,:] += sum_rows dx * acc,
- *   dbias[b,:] += sum_rows dacc  (optional: per-batch partial rows of the producing projection's bias gradient).
- * Replaces ln_modulate_bwd followed by gate_residual_bwd on the same rows. */
-int mmdit_ln_modulate_bwd_gated(const void* dout, int dout_dtype, const float* x, const float* mean, const float* rstd,
-                                const float* scale, int64_t ld_mod, const float* dres,
-                                int rows, int d, int rows_per_batch,
-                                float* dx, float* dscale, float* dshift, int64_t ld_dmod,
-                                const void* acc, int acc_dtype, const float* gate, int64_t ld_gate,
-                                void* dacc, float* dgate, int64_t ld_dgate, float* dbias, int64_t ld_dbias, mmdit_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Text pre-norm: out = scalar * RMSNorm_w(x), eps = FLT_EPSILON (nn.RMSNorm(eps=None) on fp32)
@@ -309,37 +291,28 @@ int mmdit_text_rmsnorm_bwd(const void* dout1, const void* dout2, int dout_dtype,
  * Writes bf16 Q,K,V of shape (batch, heads, S_total, 64) at token offset tok0.
  * rope_cos/rope_sin: fp32 (tokens, 64) tables or NULL (text stream: no rotation).
  * bwd: dqkv from dQ,dK,dV (dtype dq_dtype), dwq/dwk (64) accumulated atomically.
+ * A LIST of count = 1 or 2 problems per launch (else MMDIT_ERR_ARG, nothing is launched): two are the image and the text rows of a block, which
+ * write / read the same joint Q, K, V at their own token offset -- the arithmetic of two launches of one, one ramp-up and tail.
  * ------------------------------------------------------------------------- */
-int mmdit_qk_norm_rope_fwd(const void* qkv, int qkv_dtype, const float* wq, const float* wk,
-                           const float* rope_cos, const float* rope_sin,
-                           int batch, int tokens, int heads, int s_total, int tok0,
-                           void* Q, void* K, void* V, mmdit_stream_t stream);
-int mmdit_qk_norm_rope_bwd(const void* dQ, const void* dK, const void* dV, int dq_dtype,
-                           const void* qkv, int qkv_dtype, const float* wq, const float* wk,
-                           const float* rope_cos, const float* rope_sin,
-                           int batch, int tokens, int heads, int s_total, int tok0,
-                           void* dqkv, int dqkv_dtype, float* dwq, float* dwk, mmdit_stream_t stream);
-/* The image and the text rows of a block in ONE launch (both write / read the same joint Q, K, V at their own token offset; the text
- * problem has rope_cos = rope_sin = NULL): same arithmetic as two mmdit_qk_norm_rope_fwd / _bwd calls, one ramp-up and tail. */
 typedef struct mmdit_qk_problem {
   const void* qkv; const float* wq; const float* wk; const float* rope_cos; const float* rope_sin; int tokens, tok0;
   void* dqkv; float* dwq; float* dwk;      /* backward only */
 } mmdit_qk_problem;
-int mmdit_qk_norm_rope_fwd_pair(const mmdit_qk_problem* p0, const mmdit_qk_problem* p1, int qkv_dtype, int batch, int heads, int s_total,
-                                void* Q, void* K, void* V, mmdit_stream_t stream);
-int mmdit_qk_norm_rope_bwd_pair(const mmdit_qk_problem* p0, const mmdit_qk_problem* p1, const void* dQ, const void* dK, const void* dV, int dq_dtype,
-                                int qkv_dtype, int dqkv_dtype, int batch, int heads, int s_total, mmdit_stream_t stream);
+int mmdit_qk_norm_rope_fwd(const mmdit_qk_problem* probs, int count, int qkv_dtype, int batch, int heads, int s_total,
+                           void* Q, void* K, void* V, mmdit_stream_t stream);
+int mmdit_qk_norm_rope_bwd(const mmdit_qk_problem* probs, int count, const void* dQ, const void* dK, const void* dV, int dq_dtype,
+                           int qkv_dtype, int dqkv_dtype, int batch, int heads, int s_total, mmdit_stream_t stream);
 /* kv_merge_attn (Attention.py:243-251): the same launches with the keys and values of adjacent token pairs averaged.  After the norm and
  * (image stream) the rotation of EACH token in fp32, K'[j] = (K[2j] + K[2j+1]) / 2 is rounded to bf16 once; V'[j] = (V[2j] + V[2j+1]) / 2 of
  * the raw rows.  Pairs are adjacent in the flattened token order of their stream.  Q (batch, heads, s_total, 64) is written as by
- * mmdit_qk_norm_rope_fwd_pair, bit for bit; K and V are (batch, heads, s_total / 2, 64), pair j of a stream at row tok0 / 2 + j.
+ * mmdit_qk_norm_rope_fwd, bit for bit; K and V are (batch, heads, s_total / 2, 64), pair j of a stream at row tok0 / 2 + j.
  * bwd: dQ (batch, heads, s_total, 64), dK / dV (batch, heads, s_total / 2, 64): every token of a pair receives half of its merged row's
- * gradient, pushed through that token's own RoPE / norm backward; dqkv rows and the accumulated dwq / dwk as in mmdit_qk_norm_rope_bwd_pair.
+ * gradient, pushed through that token's own RoPE / norm backward; dqkv rows and the accumulated dwq / dwk as in mmdit_qk_norm_rope_bwd.
  * An odd tokens, tok0 or s_total: MMDIT_ERR_SHAPE, nothing is launched.  heads <= 21 (one pair per workgroup of 24 * heads <= 512 threads). */
-int mmdit_qk_norm_rope_fwd_merge_pair(const mmdit_qk_problem* p0, const mmdit_qk_problem* p1, int qkv_dtype, int batch, int heads, int s_total,
-                                      void* Q, void* K, void* V, mmdit_stream_t stream);
-int mmdit_qk_norm_rope_bwd_merge_pair(const mmdit_qk_problem* p0, const mmdit_qk_problem* p1, const void* dQ, const void* dK, const void* dV, int dq_dtype,
-                                      int qkv_dtype, int dqkv_dtype, int batch, int heads, int s_total, mmdit_stream_t stream);
+int mmdit_qk_norm_rope_fwd_merge(const mmdit_qk_problem* probs, int count, int qkv_dtype, int batch, int heads, int s_total,
+                                 void* Q, void* K, void* V, mmdit_stream_t stream);
+int mmdit_qk_norm_rope_bwd_merge(const mmdit_qk_problem* probs, int count, const void* dQ, const void* dK, const void* dV, int dq_dtype,
+                                 int qkv_dtype, int dqkv_dtype, int batch, int heads, int s_total, mmdit_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Joint softmax attention core, non-causal, head_dim 64, bf16 operands, fp32 accumulate.
@@ -369,7 +342,7 @@ int mmdit_attn_bwd(const void* Q, const void* K, const void* V, const void* Ox, 
                    int batch, int heads, int S, int n_img, float scale,
                    void* dQ, void* dK, void* dV, int dq_dtype, mmdit_stream_t stream);
 /* The same attention with a key length of its own (Attention.py:243-251, kv_merge_attn: S queries against the s_kv = S / 2 pair-averaged
- * keys and values of mmdit_qk_norm_rope_fwd_merge_pair).  Q, dQ: (batch, heads, S, 64); K, V, dK, dV: (batch, heads, s_kv, 64); Ox / Oc / lse /
+ * keys and values of mmdit_qk_norm_rope_fwd_merge).  Q, dQ: (batch, heads, S, 64); K, V, dK, dV: (batch, heads, s_kv, 64); Ox / Oc / lse /
  * delta and the n_img split are query-side and keep their shapes.  Any 1 <= s_kv <= S (else MMDIT_ERR_SHAPE, nothing is launched); keys of
  * the partial last tile are masked, no load leaves the operands.  s_kv == S: the results of mmdit_attn_fwd / mmdit_attn_bwd, bit for bit. */
 int mmdit_attn_fwd_kv(const void* Q, const void* K, const void* V, int batch, int heads, int S, int s_kv, int n_img,
@@ -382,16 +355,14 @@ int mmdit_attn_bwd_kv(const void* Q, const void* K, const void* V, const void* O
 /* ---------------------------------------------------------------------------
  * MLP activations.  swiglu: h = silu(g) * u with [g | u] = gu (rows, 2*hidden)  (xformers SwiGLU
  * eager semantics behind MLP.py:19,32).  gelu: h = gelu_erf(u) (MLP.py:21-23,36-40).
- * bwd also accumulates the column sums of the produced gradient into dbias (bias grad of the
- * preceding Linear), atomically; dbias may be NULL.
+ * bwd (gelu != 0: the GELU form) also accumulates the column sums of the produced gradient into dbias (bias grad of the
+ * preceding Linear), atomically; dbias may be NULL.  It takes a LIST of count = 1 or 2 problems of the same hidden width and dtype --
+ * two are the image and the text MLP of a block -- in one launch (else MMDIT_ERR_ARG, nothing is launched).
  * ------------------------------------------------------------------------- */
 int mmdit_swiglu_fwd(const void* gu, void* h, int dtype, int rows, int hidden, mmdit_stream_t stream);
-int mmdit_swiglu_bwd(const void* dh, const void* gu, void* dgu, int dtype, int rows, int hidden, float* dbias, mmdit_stream_t stream);
 int mmdit_gelu_fwd(const void* u, void* h, int dtype, int rows, int hidden, mmdit_stream_t stream);
-int mmdit_gelu_bwd(const void* dh, const void* u, void* du, int dtype, int rows, int hidden, float* dbias, mmdit_stream_t stream);
-/* mmdit_swiglu_bwd / mmdit_gelu_bwd (gelu != 0) of two problems of the same hidden width -- the image and the text MLP of a block -- in one launch */
 typedef struct mmdit_mlp_bwd_problem { const void* dh; const void* gu; void* dgu; int rows; float* dbias; } mmdit_mlp_bwd_problem;
-int mmdit_mlp_act_bwd_pair(const mmdit_mlp_bwd_problem* p0, const mmdit_mlp_bwd_problem* p1, int dtype, int hidden, int gelu, mmdit_stream_t stream);
+int mmdit_mlp_act_bwd(const mmdit_mlp_bwd_problem* probs, int count, int dtype, int hidden, int gelu, mmdit_stream_t stream);
 /* d(pre) = dy * silu'(pre): y_proj's SiLU (Transformer_Block_Dual.py:25-28). dbias accumulates column sums. */
 int mmdit_silu_bwd(const void* dy, int dy_dtype, const float* pre, void* dpre, int dpre_dtype, int rows, int cols, float* dbias, int rows_per_bias,
                    mmdit_stream_t stream);   /* rows_per_bias > 0: dbias is (rows / rows_per_bias, cols), one row per group of rows (stacked blocks) */

@@ -98,31 +98,24 @@ _SIGNATURES = {
     "mmdit_swiglu_fwd_mx": ([_vp, _i, _i, _i, _vp, _vp, _vp], _i),
     "mmdit_attn_fwd_mx": ([_vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_float, _vp, _vp, _vp, _vp, _vp], _i),
     "mmdit_cast": ([_vp, _i, _vp, _i, _i64, _vp], _i),
-    "mmdit_ln_modulate_fwd": ([_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i, _vp, _vp, _vp], _i),
-    "mmdit_ln_modulate_fwd_res": ([_vp, _vp, _i, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i, _vp, _vp, _vp], _i),
-    "mmdit_ln_modulate_fwd_pair": ([ctypes.POINTER(LnFwdProblem), ctypes.POINTER(LnFwdProblem), _i, _i, _i, _vp], _i),
-    "mmdit_ln_modulate_bwd_pair": ([ctypes.POINTER(LnBwdProblem), ctypes.POINTER(LnBwdProblem), _i, _i, _vp], _i),
-    "mmdit_qk_norm_rope_fwd_pair": ([ctypes.POINTER(QkProblem), ctypes.POINTER(QkProblem), _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
-    "mmdit_qk_norm_rope_bwd_pair": ([ctypes.POINTER(QkProblem), ctypes.POINTER(QkProblem), _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
-    "mmdit_qk_norm_rope_fwd_merge_pair": ([ctypes.POINTER(QkProblem), ctypes.POINTER(QkProblem), _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
-    "mmdit_qk_norm_rope_bwd_merge_pair": ([ctypes.POINTER(QkProblem), ctypes.POINTER(QkProblem), _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
-    "mmdit_mlp_act_bwd_pair": ([ctypes.POINTER(MlpBwdProblem), ctypes.POINTER(MlpBwdProblem), _i, _i, _i, _vp], _i),
+    # the row operations that take a list (array pointer, count = 1 or 2) of problem structs
+    "mmdit_ln_modulate_fwd": ([ctypes.POINTER(LnFwdProblem), _i, _i, _i, _i, _vp], _i),
+    "mmdit_ln_modulate_bwd": ([ctypes.POINTER(LnBwdProblem), _i, _i, _i, _vp], _i),
+    "mmdit_qk_norm_rope_fwd": ([ctypes.POINTER(QkProblem), _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "mmdit_qk_norm_rope_bwd": ([ctypes.POINTER(QkProblem), _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
+    "mmdit_qk_norm_rope_fwd_merge": ([ctypes.POINTER(QkProblem), _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "mmdit_qk_norm_rope_bwd_merge": ([ctypes.POINTER(QkProblem), _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
+    "mmdit_mlp_act_bwd": ([ctypes.POINTER(MlpBwdProblem), _i, _i, _i, _i, _vp], _i),
     "mmdit_gate_residual_fwd": ([_vp, _vp, _i, _vp, _i64, _i, _i, _i, _vp, _vp], _i),
-    "mmdit_ln_modulate_bwd": ([_vp, _i, _vp, _vp, _vp, _vp, _i64, _vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp], _i),
-    "mmdit_ln_modulate_bwd_gated": ([_vp, _i, _vp, _vp, _vp, _vp, _i64, _vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _i, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp], _i),
     "mmdit_text_rmsnorm_fwd": ([_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp], _i),
     "mmdit_text_rmsnorm_bwd": ([_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
-    "mmdit_qk_norm_rope_fwd": ([_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
-    "mmdit_qk_norm_rope_bwd": ([_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp], _i),
     "mmdit_attn_fwd": ([_vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp], _i),
     "mmdit_attn_bwd_qk": ([_vp] * 9 + [_i, _i, _i, _i, _f] + [_vp] * 11 + [_vp], _i),
     "mmdit_attn_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp], _i),
     "mmdit_attn_fwd_kv": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp], _i),
     "mmdit_attn_bwd_kv": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp], _i),
     "mmdit_swiglu_fwd": ([_vp, _vp, _i, _i, _i, _vp], _i),
-    "mmdit_swiglu_bwd": ([_vp, _vp, _vp, _i, _i, _i, _vp, _vp], _i),
     "mmdit_gelu_fwd": ([_vp, _vp, _i, _i, _i, _vp], _i),
-    "mmdit_gelu_bwd": ([_vp, _vp, _vp, _i, _i, _i, _vp, _vp], _i),
     "mmdit_silu_bwd": ([_vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp], _i),
     "mmdit_gate_residual_bwd": ([_vp, _vp, _i, _vp, _i64, _i, _i, _i, _vp, _i, _vp, _i64, _vp, _i64, _vp], _i),
     "mmdit_flow_loss": ([_vp, _vp, _vp, _i, _i64, _f, _vp, _vp, _vp, _vp], _i),
@@ -145,7 +138,7 @@ _SIGNATURES = {
     "mmdit_cast_multi": ([_vp, _vp, _vp, _i, _vp], _i),
 }
 ADAMW_CHUNK = 65536   # MMDIT_ADAMW_CHUNK
-ABI_VERSION = 9       # MMDIT_ABI_VERSION of include/mmdit_hip.h this binding mirrors
+ABI_VERSION = 10      # MMDIT_ABI_VERSION of include/mmdit_hip.h this binding mirrors
 # struct ids of mmdit_struct_size() -> ctypes mirrors (None: laid out with numpy record dtypes in optim.py / ops.py: 48 / 24 bytes)
 _STRUCTS = [("mmdit_gemm_args", GemmArgs), ("mmdit_ln_fwd_problem", LnFwdProblem), ("mmdit_ln_bwd_problem", LnBwdProblem),
             ("mmdit_qk_problem", QkProblem), ("mmdit_mlp_bwd_problem", MlpBwdProblem), ("mmdit_adamw_tensor", None), ("mmdit_cast_tensor", None), ("mmdit_qk_epilogue", QkEpilogue)]

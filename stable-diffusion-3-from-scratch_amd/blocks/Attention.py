@@ -3,7 +3,7 @@ configuration (dual stream, attn_type softmax / softmax_flash, RoPE2d, non-causa
 forward 118-135, 174-194, 258-293, 410-425).  Experimental attention types of the reference
 (cosine*, relu, silu, exp, both, qk_half_dim, 1-D RoPE, RoPE2dV2) are out of scope and
 raise.  kv_merge_attn (243-251) is implemented: the keys / values of adjacent token pairs of each stream are
-averaged (mmdit_qk_norm_rope_fwd_merge_pair) and S queries attend to S / 2 keys (mmdit_attn_fwd_kv)."""
+averaged (mmdit_qk_norm_rope_fwd_merge) and S queries attend to S / 2 keys (mmdit_attn_fwd_kv)."""
 from types import SimpleNamespace as NS
 
 import torch

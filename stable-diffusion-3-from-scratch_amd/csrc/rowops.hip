@@ -95,28 +95,21 @@ __device__ __forceinline__ void ln_mod_fwd_body(int block, const float* __restri
   }
 }
 
-template <int NIT, typename TO, typename TA, bool RES, bool MX = false>
-__global__ __launch_bounds__(256) void ln_mod_fwd_kernel(const float* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ shift,
-                                                         int64_t ld_mod, int rows, int d, int rpb, TO* __restrict__ out,
-                                                         float* __restrict__ mean_o, float* __restrict__ rstd_o,
-                                                         const TA* __restrict__ acc, const float* __restrict__ gate, int64_t ld_gate, float* __restrict__ xo,
-                                                         unsigned char* __restrict__ mx_scales = nullptr) {
-  ln_mod_fwd_body<NIT, TO, TA, RES, MX>((int)blockIdx.x, x, scale, shift, ld_mod, rows, d, rpb, out, mean_o, rstd_o, acc, gate, ld_gate, xo, mx_scales);
-}
-
-// Two independent adaLN problems of the same width in ONE launch (the image and the text stream of a block): these kernels run 20-45 us
-// on 75-180 MB, of which ~8 us is ramp-up and tail -- one launch over both streams instead of two saves ~5 us per pair
-// (tools/row_bench.py --cold).  Blocks [0, nblk0) work on problem 0, the rest on problem 1.
+// The __global__ wrappers of the row operations below (adaLN, QK-norm + RoPE, kv-merge, MLP activation backward) take a LIST of one or two
+// independent problems of the same width and dtypes in ONE launch: blocks [0, nblk0) (g0, nby0) work on problem 0, the rest on problem 1.  A
+// list of one passes nblk0 = the whole grid and a zero-initialised second problem.  Two problems are the image and the text stream of a block:
+// these kernels run 20-45 us on 75-180 MB, of which ~8 us is ramp-up and tail -- one launch over both streams instead of two saves ~5 us per
+// pair (tools/row_bench.py --cold).  The work itself is in the __device__ bodies, which know nothing of the list.
 struct LnFwdProb {
   const float* x; const float* scale; const float* shift; int64_t ld_mod; int rows, rpb; void* out; float* mean; float* rstd;
-  const void* acc; const float* gate; int64_t ld_gate; float* xo;
+  const void* acc; const float* gate; int64_t ld_gate; float* xo; unsigned char* mx_scales;
 };
-template <int NIT, typename TO, typename TA, bool RES>
-__global__ __launch_bounds__(256) void ln_mod_fwd_pair_kernel(LnFwdProb p0, LnFwdProb p1, int nblk0, int d) {
+template <int NIT, typename TO, typename TA, bool RES, bool MX = false>
+__global__ __launch_bounds__(256) void ln_mod_fwd_kernel(LnFwdProb p0, LnFwdProb p1, int nblk0, int d) {
   const bool first = (int)blockIdx.x < nblk0;     // (workgroup-uniform)
   const LnFwdProb& p = first ? p0 : p1;
-  ln_mod_fwd_body<NIT, TO, TA, RES, false>(first ? (int)blockIdx.x : (int)blockIdx.x - nblk0, p.x, p.scale, p.shift, p.ld_mod, p.rows, d, p.rpb, (TO*)p.out, p.mean, p.rstd,
-                                           (const TA*)p.acc, p.gate, p.ld_gate, p.xo, nullptr);
+  ln_mod_fwd_body<NIT, TO, TA, RES, MX>(first ? (int)blockIdx.x : (int)blockIdx.x - nblk0, p.x, p.scale, p.shift, p.ld_mod, p.rows, d, p.rpb, (TO*)p.out, p.mean, p.rstd,
+                                        (const TA*)p.acc, p.gate, p.ld_gate, p.xo, p.mx_scales);
 }
 
 // out = x + gate[b] * acc (the gated residual update on its own: used where no norm consumes the result)
@@ -260,25 +253,14 @@ __device__ __forceinline__ void ln_mod_bwd_body(int block, const TG* __restrict_
   }
 }
 
-template <int NIT, typename TG, typename TA, bool GATED>
-__global__ __launch_bounds__(256) void ln_mod_bwd_kernel(const TG* __restrict__ dout, const float* __restrict__ x, const float* __restrict__ mean_i,
-                                                         const float* __restrict__ rstd_i, const float* __restrict__ scale, int64_t ld_mod,
-                                                         const float* __restrict__ dres, int d, int rpb, int nchunk,
-                                                         float* __restrict__ dx, float* __restrict__ dscale, float* __restrict__ dshift, int64_t ld_dmod,
-                                                         const TA* __restrict__ acc, const float* __restrict__ gate, int64_t ld_gate, TA* __restrict__ dacc,
-                                                         float* __restrict__ dgate, int64_t ld_dgate, float* __restrict__ dbias, int64_t ld_dbias) {
-  ln_mod_bwd_body<NIT, TG, TA, GATED>((int)blockIdx.x, dout, x, mean_i, rstd_i, scale, ld_mod, dres, d, rpb, nchunk, dx, dscale, dshift, ld_dmod, acc, gate, ld_gate, dacc,
-                                      dgate, ld_dgate, dbias, ld_dbias);
-}
-
-// two adaLN backward problems of the same width in one launch (see ln_mod_fwd_pair_kernel)
+// a list of one or two adaLN backward problems of the same width (see ln_mod_fwd_kernel); rch rows per workgroup
 struct LnBwdProb {
   const void* dout; const float* x; const float* mean; const float* rstd; const float* scale; int64_t ld_mod; const float* dres; int rpb, nchunk;   // nchunk chunks of rch rows per sample
   float* dx; float* dscale; float* dshift; int64_t ld_dmod;
   const void* acc; const float* gate; int64_t ld_gate; void* dacc; float* dgate; int64_t ld_dgate; float* dbias; int64_t ld_dbias;
 };
 template <int NIT, typename TG, typename TA, bool GATED>
-__global__ __launch_bounds__(256) void ln_mod_bwd_pair_kernel(LnBwdProb p0, LnBwdProb p1, int nblk0, int d, int rch) {
+__global__ __launch_bounds__(256) void ln_mod_bwd_kernel(LnBwdProb p0, LnBwdProb p1, int nblk0, int d, int rch) {
   const bool first = (int)blockIdx.x < nblk0;     // (workgroup-uniform)
   const LnBwdProb& p = first ? p0 : p1;
   ln_mod_bwd_body<NIT, TG, TA, GATED>(first ? (int)blockIdx.x : (int)blockIdx.x - nblk0, (const TG*)p.dout, p.x, p.mean, p.rstd, p.scale, p.ld_mod, p.dres, d, p.rpb, p.nchunk,
@@ -409,7 +391,7 @@ __device__ __forceinline__ float group8_sum(float v) {
 // head, 8-element chunk), no per-element index divisions, norm weights in registers), rows blockIdx.x, + gridDim.x, ... two in
 // flight; with the grid a multiple of the tokens per sample all rows of a workgroup are the same token and the RoPE factors are
 // loaded once.
-// (bid, rstride) = this workgroup's index and the number of workgroups of ITS problem (the pair kernel runs two problems in one grid)
+// (bid, rstride) = this workgroup's index and the number of workgroups of ITS problem (the kernel runs a list of problems in one grid)
 template <typename TI>
 __device__ __forceinline__ void qk_norm_rope_fwd_body(int bid, int rstride, const TI* __restrict__ qkv, const float* __restrict__ wq, const float* __restrict__ wk,
                                                       const float* __restrict__ rcos, const float* __restrict__ rsin,
@@ -472,21 +454,14 @@ __device__ __forceinline__ void qk_norm_rope_fwd_body(int bid, int rstride, cons
     }
   }
 }
-template <typename TI>
-__global__ __launch_bounds__(1024) void qk_norm_rope_fwd_kernel(const TI* __restrict__ qkv, const float* __restrict__ wq, const float* __restrict__ wk,
-                                                                const float* __restrict__ rcos, const float* __restrict__ rsin,
-                                                                int rows, int tokens, int heads, int s_total, int tok0,
-                                                                bf16_t* __restrict__ Q, bf16_t* __restrict__ K, bf16_t* __restrict__ V) {
-  qk_norm_rope_fwd_body<TI>((int)blockIdx.x, (int)gridDim.x, qkv, wq, wk, rcos, rsin, rows, tokens, heads, s_total, tok0, Q, K, V);
-}
-// the image and the text rows of a block in one launch (workgroups [0, g0) = problem 0): same Q / K / V, different token ranges
+// a list of one or two problems (workgroups [0, g0) = problem 0): the image and the text rows of a block write the same Q / K / V, different token ranges
 struct QkProb {
   const void* qkv; const float* wq; const float* wk; const float* rcos; const float* rsin; int rows, tokens, tok0;
   const void* dQ; const void* dK; const void* dV; void* dqkv; float* dwq; float* dwk;      // (backward only)
 };
 template <typename TI>
-__global__ __launch_bounds__(1024) void qk_norm_rope_fwd_pair_kernel(QkProb p0, QkProb p1, int g0, int heads, int s_total,
-                                                                     bf16_t* __restrict__ Q, bf16_t* __restrict__ K, bf16_t* __restrict__ V) {
+__global__ __launch_bounds__(1024) void qk_norm_rope_fwd_kernel(QkProb p0, QkProb p1, int g0, int heads, int s_total,
+                                                                bf16_t* __restrict__ Q, bf16_t* __restrict__ K, bf16_t* __restrict__ V) {
   const bool first = (int)blockIdx.x < g0;     // (workgroup-uniform)
   const QkProb& p = first ? p0 : p1;
   qk_norm_rope_fwd_body<TI>(first ? (int)blockIdx.x : (int)blockIdx.x - g0, first ? g0 : (int)gridDim.x - g0, (const TI*)p.qkv, p.wq, p.wk, p.rcos, p.rsin,
@@ -594,15 +569,7 @@ __device__ __forceinline__ void qk_norm_rope_bwd_body(int bid, int rstride, cons
   for (int i = threadIdx.x; i < 128; i += blockDim.x) atomicAdd((i < 64 ? dwq : dwk) + (i & 63), sdw[i >> 6][i & 63]);
 }
 template <bool FAST, typename TG, typename TI, typename TO>
-__global__ __launch_bounds__(1024) void qk_norm_rope_bwd_kernel(const TG* __restrict__ dQ, const TG* __restrict__ dK, const TG* __restrict__ dV,
-                                                                const TI* __restrict__ qkv, const float* __restrict__ wq, const float* __restrict__ wk,
-                                                                const float* __restrict__ rcos, const float* __restrict__ rsin,
-                                                                int rows, int tokens, int heads, int s_total, int tok0,
-                                                                TO* __restrict__ dqkv, float* __restrict__ dwq, float* __restrict__ dwk) {
-  qk_norm_rope_bwd_body<FAST, TG, TI, TO>((int)blockIdx.x, (int)gridDim.x, dQ, dK, dV, qkv, wq, wk, rcos, rsin, rows, tokens, heads, s_total, tok0, dqkv, dwq, dwk);
-}
-template <bool FAST, typename TG, typename TI, typename TO>
-__global__ __launch_bounds__(1024) void qk_norm_rope_bwd_pair_kernel(QkProb p0, QkProb p1, int g0, int heads, int s_total) {
+__global__ __launch_bounds__(1024) void qk_norm_rope_bwd_kernel(QkProb p0, QkProb p1, int g0, int heads, int s_total) {
   const bool first = (int)blockIdx.x < g0;     // (workgroup-uniform)
   const QkProb& p = first ? p0 : p1;
   qk_norm_rope_bwd_body<FAST, TG, TI, TO>(first ? (int)blockIdx.x : (int)blockIdx.x - g0, first ? g0 : (int)gridDim.x - g0, (const TG*)p.dQ, (const TG*)p.dK, (const TG*)p.dV,
@@ -672,8 +639,8 @@ __device__ __forceinline__ void qk_merge_fwd_body(int bid, int pstride, const TI
   }
 }
 template <typename TI>
-__global__ __launch_bounds__(512) void qk_merge_fwd_pair_kernel(QkProb p0, QkProb p1, int g0, int heads, int s_total,
-                                                                 bf16_t* __restrict__ Q, bf16_t* __restrict__ K, bf16_t* __restrict__ V) {
+__global__ __launch_bounds__(512) void qk_merge_fwd_kernel(QkProb p0, QkProb p1, int g0, int heads, int s_total,
+                                                            bf16_t* __restrict__ Q, bf16_t* __restrict__ K, bf16_t* __restrict__ V) {
   const bool first = (int)blockIdx.x < g0;     // (workgroup-uniform)
   const QkProb& p = first ? p0 : p1;
   qk_merge_fwd_body<TI>(first ? (int)blockIdx.x : (int)blockIdx.x - g0, first ? g0 : (int)gridDim.x - g0, (const TI*)p.qkv, p.wq, p.wk, p.rcos, p.rsin,
@@ -754,7 +721,7 @@ __device__ __forceinline__ void qk_merge_bwd_body(int bid, int pstride, const TG
   for (int i = threadIdx.x; i < 128; i += blockDim.x) atomicAdd((i < 64 ? dwq : dwk) + (i & 63), sdw[i >> 6][i & 63]);
 }
 template <typename TG, typename TI, typename TO>
-__global__ __launch_bounds__(512) void qk_merge_bwd_pair_kernel(QkProb p0, QkProb p1, int g0, int heads, int s_total) {
+__global__ __launch_bounds__(512) void qk_merge_bwd_kernel(QkProb p0, QkProb p1, int g0, int heads, int s_total) {
   const bool first = (int)blockIdx.x < g0;     // (workgroup-uniform)
   const QkProb& p = first ? p0 : p1;
   qk_merge_bwd_body<TG, TI, TO>(first ? (int)blockIdx.x : (int)blockIdx.x - g0, first ? g0 : (int)gridDim.x - g0, (const TG*)p.dQ, (const TG*)p.dK, (const TG*)p.dV,
@@ -895,15 +862,10 @@ __device__ __forceinline__ void mlp_act_bwd_body(int by, const T* __restrict__ d
     }
   }
 }
-template <typename T, bool GELU>
-__global__ __launch_bounds__(256) void mlp_act_bwd_kernel(const T* __restrict__ dh, const T* __restrict__ gu, T* __restrict__ dgu,
-                                                          int rows, int hidden, float* __restrict__ dbias) {
-  mlp_act_bwd_body<T, GELU>((int)blockIdx.y, dh, gu, dgu, rows, hidden, dbias);
-}
-// two problems of the same hidden width (the image and the text MLP of a block) in one launch: blockIdx.y in [0, nby0) = problem 0
+// a list of one or two problems of the same hidden width (the image and the text MLP of a block): blockIdx.y in [0, nby0) = problem 0
 struct MlpBwdProb { const void* dh; const void* gu; void* dgu; int rows; float* dbias; };
 template <typename T, bool GELU>
-__global__ __launch_bounds__(256) void mlp_act_bwd_pair_kernel(MlpBwdProb p0, MlpBwdProb p1, int nby0, int hidden) {
+__global__ __launch_bounds__(256) void mlp_act_bwd_kernel(MlpBwdProb p0, MlpBwdProb p1, int nby0, int hidden) {
   const bool first = (int)blockIdx.y < nby0;     // (workgroup-uniform)
   const MlpBwdProb& p = first ? p0 : p1;
   mlp_act_bwd_body<T, GELU>(first ? (int)blockIdx.y : (int)blockIdx.y - nby0, (const T*)p.dh, (const T*)p.gu, (T*)p.dgu, p.rows, hidden, p.dbias);
@@ -1112,45 +1074,42 @@ extern "C" int mmdit_struct_size(int which) {
 }
 extern "C" const char* mmdit_build_arch(void) { return "gfx950"; }
 
-extern "C" int mmdit_ln_modulate_fwd(const float* x, const float* scale, const float* shift, int64_t ld_mod, int rows, int d, int rpb,
-                                     void* out, int out_dtype, float* mean, float* rstd, mmdit_stream_t stream) {
-  MMDIT_CHECK_ARG(x && scale && shift && out && mean && rstd && rows > 0 && d > 0 && d % 4 == 0 && d <= 4096 && rpb > 0 && ld_mod % 4 == 0);
-  hipStream_t s = (hipStream_t)stream;
+// One launch over a list of 1 or 2 adaLN forward problems; mx_scales != NULL: the MX-emitting form (a list of one, bf16 acc).
+static int ln_mod_fwd_launch(const mmdit_ln_fwd_problem* probs, int count, int d, int out_dtype, unsigned char* mx_scales, hipStream_t s) {
+  MMDIT_CHECK_ARG(probs && count >= 1 && count <= 2 && d > 0 && d % 4 == 0 && d <= 4096);
+  const bool res = probs[0].acc != nullptr;
+  LnFwdProb q[2] = {};
+  int nb[2] = {0, 0};
+  for (int i = 0; i < count; i++) {
+    const mmdit_ln_fwd_problem* p = probs + i;
+    MMDIT_CHECK_ARG((p->acc != nullptr) == res);
+    MMDIT_CHECK_ARG(p->x && p->scale && p->shift && p->out && p->mean && p->rstd && p->rows > 0 && p->rows_per_batch > 0 && p->ld_mod % 4 == 0);
+    if (res) MMDIT_CHECK_ARG(p->gate && p->x_out && p->ld_gate % 4 == 0);
+    q[i] = LnFwdProb{p->x, p->scale, p->shift, p->ld_mod, p->rows, p->rows_per_batch, p->out, p->mean, p->rstd, p->acc, p->gate, p->ld_gate, p->x_out, mx_scales};
+    nb[i] = (p->rows + 3) / 4;
+  }
   const int nit = nit_for(d);
-  dim3 grid((rows + 3) / 4);
-  if (out_dtype == MMDIT_BF16) { NIT_SWITCH(nit, hipLaunchKernelGGL((ln_mod_fwd_kernel<LN_FWD_NIT, bf16_t, bf16_t, false>), grid, dim3(256), 0, s, x, scale, shift, ld_mod, rows, d, rpb, (bf16_t*)out, mean, rstd, nullptr, nullptr, 0, nullptr)); }
-  else if (out_dtype == MMDIT_F32) { NIT_SWITCH(nit, hipLaunchKernelGGL((ln_mod_fwd_kernel<LN_FWD_NIT, float, float, false>), grid, dim3(256), 0, s, x, scale, shift, ld_mod, rows, d, rpb, (float*)out, mean, rstd, nullptr, nullptr, 0, nullptr)); }
+  dim3 grid(nb[0] + nb[1]);
+#define LNL(TO, TA, RES, MX) NIT_SWITCH(nit, hipLaunchKernelGGL((ln_mod_fwd_kernel<LN_FWD_NIT, TO, TA, RES, MX>), grid, dim3(256), 0, s, q[0], q[1], nb[0], d))
+  if (mx_scales) { if (res) { LNL(unsigned char, bf16_t, true, true); } else { LNL(unsigned char, bf16_t, false, true); } }
+  else if (out_dtype == MMDIT_BF16) { if (res) { LNL(bf16_t, bf16_t, true, false); } else { LNL(bf16_t, bf16_t, false, false); } }
+  else if (out_dtype == MMDIT_F32) { if (res) { LNL(float, float, true, false); } else { LNL(float, float, false, false); } }
   else return MMDIT_ERR_DTYPE;
+#undef LNL
   return mmdit_launch_status();
 }
 
-extern "C" int mmdit_ln_modulate_fwd_res(const float* x, const void* acc, int acc_dtype, const float* gate, int64_t ld_gate, float* x_out,
-                                         const float* scale, const float* shift, int64_t ld_mod, int rows, int d, int rpb,
-                                         void* out, int out_dtype, float* mean, float* rstd, mmdit_stream_t stream) {
-  MMDIT_CHECK_ARG(x && acc && gate && x_out && scale && shift && out && mean && rstd && rows > 0 && d > 0 && d % 4 == 0 && d <= 4096 && rpb > 0 && ld_mod % 4 == 0 && ld_gate % 4 == 0);
-  MMDIT_CHECK_ARG(acc_dtype == out_dtype);
-  hipStream_t s = (hipStream_t)stream;
-  const int nit = nit_for(d);
-  dim3 grid((rows + 3) / 4);
-  if (out_dtype == MMDIT_BF16) { NIT_SWITCH(nit, hipLaunchKernelGGL((ln_mod_fwd_kernel<LN_FWD_NIT, bf16_t, bf16_t, true>), grid, dim3(256), 0, s, x, scale, shift, ld_mod, rows, d, rpb, (bf16_t*)out, mean, rstd, (const bf16_t*)acc, gate, ld_gate, x_out)); }
-  else if (out_dtype == MMDIT_F32) { NIT_SWITCH(nit, hipLaunchKernelGGL((ln_mod_fwd_kernel<LN_FWD_NIT, float, float, true>), grid, dim3(256), 0, s, x, scale, shift, ld_mod, rows, d, rpb, (float*)out, mean, rstd, (const float*)acc, gate, ld_gate, x_out)); }
-  else return MMDIT_ERR_DTYPE;
-  return mmdit_launch_status();
+extern "C" int mmdit_ln_modulate_fwd(const mmdit_ln_fwd_problem* probs, int count, int d, int acc_dtype, int out_dtype, mmdit_stream_t stream) {
+  MMDIT_CHECK_ARG(probs && count >= 1 && (!probs[0].acc || acc_dtype == out_dtype));
+  return ln_mod_fwd_launch(probs, count, d, out_dtype, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int mmdit_ln_modulate_fwd_mx(const float* x, const void* acc, int acc_dtype, const float* gate, int64_t ld_gate, float* x_out,
                                         const float* scale, const float* shift, int64_t ld_mod, int rows, int d, int rpb,
                                         void* q_fp8, void* scales_e8m0, float* mean, float* rstd, mmdit_stream_t stream) {
-  MMDIT_CHECK_ARG(x && scale && shift && q_fp8 && scales_e8m0 && mean && rstd && rows > 0 && d > 0 && d % 64 == 0 && d <= 4096 && rpb > 0 && ld_mod % 4 == 0);
-  MMDIT_CHECK_ARG(!acc || (gate && x_out && acc_dtype == MMDIT_BF16 && ld_gate % 4 == 0));
-  hipStream_t s = (hipStream_t)stream;
-  const int nit = nit_for(d);
-  dim3 grid((rows + 3) / 4);
-  unsigned char* q = (unsigned char*)q_fp8;
-  unsigned char* sc = (unsigned char*)scales_e8m0;
-  if (acc) { NIT_SWITCH(nit, hipLaunchKernelGGL((ln_mod_fwd_kernel<LN_FWD_NIT, unsigned char, bf16_t, true, true>), grid, dim3(256), 0, s, x, scale, shift, ld_mod, rows, d, rpb, q, mean, rstd, (const bf16_t*)acc, gate, ld_gate, x_out, sc)); }
-  else { NIT_SWITCH(nit, hipLaunchKernelGGL((ln_mod_fwd_kernel<LN_FWD_NIT, unsigned char, bf16_t, false, true>), grid, dim3(256), 0, s, x, scale, shift, ld_mod, rows, d, rpb, q, mean, rstd, nullptr, nullptr, 0, nullptr, sc)); }
-  return mmdit_launch_status();
+  MMDIT_CHECK_ARG(scales_e8m0 && d % 64 == 0 && (!acc || acc_dtype == MMDIT_BF16));
+  const mmdit_ln_fwd_problem p = {x, acc, gate, ld_gate, x_out, scale, shift, ld_mod, rows, rpb, q_fp8, mean, rstd};
+  return ln_mod_fwd_launch(&p, 1, d, MMDIT_FP8, (unsigned char*)scales_e8m0, (hipStream_t)stream);
 }
 
 extern "C" int mmdit_gate_residual_fwd(const float* x, const void* acc, int acc_dtype, const float* gate, int64_t ld_gate, int rows, int d, int rpb,
@@ -1164,73 +1123,13 @@ extern "C" int mmdit_gate_residual_fwd(const float* x, const void* acc, int acc_
   return mmdit_launch_status();
 }
 
-template <typename TG, typename TA, bool GATED>
-static int ln_mod_bwd_launch(const void* dout, const float* x, const float* mean, const float* rstd, const float* scale, int64_t ld_mod, const float* dres,
-                             int rows, int d, int rpb, float* dx, float* dscale, float* dshift, int64_t ld_dmod, const void* acc, const float* gate,
-                             int64_t ld_gate, void* dacc, float* dgate, int64_t ld_dgate, float* dbias, int64_t ld_dbias, hipStream_t s) {
-  const int nit = nit_for(d), nchunk = (rpb + LN_BWD_RCH - 1) / LN_BWD_RCH;
-  dim3 grid((rows / rpb) * nchunk);
-  NIT_SWITCH(nit, hipLaunchKernelGGL((ln_mod_bwd_kernel<(NIT < 0 ? -NIT : NIT), TG, TA, GATED>), grid, dim3(256), 0, s, (const TG*)dout, x, mean, rstd, scale, ld_mod, dres, d, rpb, nchunk,
-                                     dx, dscale, dshift, ld_dmod, (const TA*)acc, gate, ld_gate, (TA*)dacc, dgate, ld_dgate, dbias, ld_dbias));
-  return mmdit_launch_status();
-}
-
-extern "C" int mmdit_ln_modulate_bwd(const void* dout, int dout_dtype, const float* x, const float* mean, const float* rstd, const float* scale, int64_t ld_mod,
-                                     const float* dres, int rows, int d, int rpb, float* dx, float* dscale, float* dshift, int64_t ld_dmod, mmdit_stream_t stream) {
-  MMDIT_CHECK_ARG(dout && x && mean && rstd && scale && dx && dscale && dshift && rows > 0 && d % 4 == 0 && d <= 4096 && rpb > 0 && rows % rpb == 0 && ld_mod % 4 == 0);
-  hipStream_t s = (hipStream_t)stream;
-  if (dout_dtype == MMDIT_BF16) return ln_mod_bwd_launch<bf16_t, bf16_t, false>(dout, x, mean, rstd, scale, ld_mod, dres, rows, d, rpb, dx, dscale, dshift, ld_dmod, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, s);
-  if (dout_dtype == MMDIT_F32) return ln_mod_bwd_launch<float, float, false>(dout, x, mean, rstd, scale, ld_mod, dres, rows, d, rpb, dx, dscale, dshift, ld_dmod, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, s);
-  return MMDIT_ERR_DTYPE;
-}
-
-extern "C" int mmdit_ln_modulate_bwd_gated(const void* dout, int dout_dtype, const float* x, const float* mean, const float* rstd, const float* scale, int64_t ld_mod,
-                                           const float* dres, int rows, int d, int rpb, float* dx, float* dscale, float* dshift, int64_t ld_dmod,
-                                           const void* acc, int acc_dtype, const float* gate, int64_t ld_gate, void* dacc, float* dgate, int64_t ld_dgate,
-                                           float* dbias, int64_t ld_dbias, mmdit_stream_t stream) {
-  MMDIT_CHECK_ARG(dout && x && mean && rstd && scale && dx && dscale && dshift && rows > 0 && d % 4 == 0 && d <= 4096 && rpb > 0 && rows % rpb == 0 && ld_mod % 4 == 0);
-  MMDIT_CHECK_ARG(acc && gate && dacc && dgate && ld_gate % 4 == 0 && acc_dtype == dout_dtype);
-  hipStream_t s = (hipStream_t)stream;
-  if (dout_dtype == MMDIT_BF16) return ln_mod_bwd_launch<bf16_t, bf16_t, true>(dout, x, mean, rstd, scale, ld_mod, dres, rows, d, rpb, dx, dscale, dshift, ld_dmod, acc, gate, ld_gate, dacc, dgate, ld_dgate, dbias, ld_dbias, s);
-  if (dout_dtype == MMDIT_F32) return ln_mod_bwd_launch<float, float, true>(dout, x, mean, rstd, scale, ld_mod, dres, rows, d, rpb, dx, dscale, dshift, ld_dmod, acc, gate, ld_gate, dacc, dgate, ld_dgate, dbias, ld_dbias, s);
-  return MMDIT_ERR_DTYPE;
-}
-
-extern "C" int mmdit_ln_modulate_fwd_pair(const mmdit_ln_fwd_problem* a, const mmdit_ln_fwd_problem* b, int d, int acc_dtype, int out_dtype, mmdit_stream_t stream) {
-  MMDIT_CHECK_ARG(a && b && d > 0 && d % 4 == 0 && d <= 4096);
-  const bool res = a->acc != nullptr;
-  MMDIT_CHECK_ARG((b->acc != nullptr) == res && (!res || acc_dtype == out_dtype));
-  LnFwdProb q[2];
-  const mmdit_ln_fwd_problem* src[2] = {a, b};
-  for (int i = 0; i < 2; i++) {
-    const mmdit_ln_fwd_problem* p = src[i];
-    MMDIT_CHECK_ARG(p->x && p->scale && p->shift && p->out && p->mean && p->rstd && p->rows > 0 && p->rows_per_batch > 0 && p->ld_mod % 4 == 0);
-    if (res) MMDIT_CHECK_ARG(p->gate && p->x_out && p->ld_gate % 4 == 0);
-    q[i] = LnFwdProb{p->x, p->scale, p->shift, p->ld_mod, p->rows, p->rows_per_batch, p->out, p->mean, p->rstd, p->acc, p->gate, p->ld_gate, p->x_out};
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const int nit = nit_for(d), nb0 = (a->rows + 3) / 4, nb1 = (b->rows + 3) / 4;
-  dim3 grid(nb0 + nb1);
-#define LNP(TO, RES) NIT_SWITCH(nit, hipLaunchKernelGGL((ln_mod_fwd_pair_kernel<LN_FWD_NIT, TO, TO, RES>), grid, dim3(256), 0, s, q[0], q[1], nb0, d))
-  if (out_dtype == MMDIT_BF16) { if (res) { LNP(bf16_t, true); } else { LNP(bf16_t, false); } }
-  else if (out_dtype == MMDIT_F32) { if (res) { LNP(float, true); } else { LNP(float, false); } }
-  else return MMDIT_ERR_DTYPE;
-#undef LNP
-  return mmdit_launch_status();
-}
-
-extern "C" int mmdit_ln_modulate_bwd_pair(const mmdit_ln_bwd_problem* a, const mmdit_ln_bwd_problem* b, int d, int dout_dtype, mmdit_stream_t stream) {
-  MMDIT_CHECK_ARG(a && b && d > 0 && d % 4 == 0 && d <= 4096 && a->rows_per_batch > 0 && b->rows_per_batch > 0);
-  const bool gated = a->acc != nullptr;
-  MMDIT_CHECK_ARG((b->acc != nullptr) == gated);
-  LnBwdProb q[2];
-  const mmdit_ln_bwd_problem* src[2] = {a, b};
-  int nb[2];
-  // rows per workgroup: 16, or more when 16 would give more workgroups than fit the chip at once (4 of these 256-thread workgroups per CU): the
-  // image + text launch of MMDiT-B at batch 64 is 1640 workgroups of 16 rows = 1.6 rounds, 832 of 32 rows or 1024 of 28 rows = one round -- measured
-  // 68.4 (16) -> 63.8 us (32) (single-stream launches, one round either way, are faster with 16: 42 vs 47 us)
-  // (generalised: the smallest multiple of 4 rows -- one row per wave and step -- for which the launch fits the chip in ONE round; the resident
-  //  workgroups per CU follow from the kernel's registers: 4 up to d = 768, 3 at d = 1024, 2 above)
+// Rows per workgroup of a TWO-problem adaLN backward launch: 16, or more when 16 would give more workgroups than fit the chip at once (4 of these
+// 256-thread workgroups per CU): the image + text launch of MMDiT-B at batch 64 is 1640 workgroups of 16 rows = 1.6 rounds, 832 of 32 rows or 1024
+// of 28 rows = one round -- measured 68.4 (16) -> 63.8 us (32) (single-stream launches, one round either way, are faster with 16: 42 vs 47 us, and
+// keep LN_BWD_RCH)
+// (generalised: the smallest multiple of 4 rows -- one row per wave and step -- for which the launch fits the chip in ONE round; the resident
+//  workgroups per CU follow from the kernel's registers: 4 up to d = 768, 3 at d = 1024, 2 above)
+static int ln_bwd_one_round_rch(const mmdit_ln_bwd_problem* a, const mmdit_ln_bwd_problem* b, int d, int dout_dtype, bool gated) {
   auto wgs = [&](int r) { return (long)(a->rows / a->rows_per_batch) * ((a->rows_per_batch + r - 1) / r) + (long)(b->rows / b->rows_per_batch) * ((b->rows_per_batch + r - 1) / r); };
   const int nit_ = nit_for(d), nit_abs = nit_ < 0 ? -nit_ : nit_;
   // resident workgroups = CUs of THIS device x workgroups per CU.  Per CU: the measured table (4 / 3 / 2 by row width), capped by what the
@@ -1249,7 +1148,7 @@ extern "C" int mmdit_ln_modulate_bwd_pair(const mmdit_ln_bwd_problem* a, const m
     if (!occ[dev][ni][ti][gi]) {
       int nbq = 0;
       hipError_t e = hipErrorUnknown;
-#define LNQ(T, G) NIT_SWITCH(nit_, e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbq, (const void*)ln_mod_bwd_pair_kernel<(NIT < 0 ? -NIT : NIT), T, T, G>, 256, 0))
+#define LNQ(T, G) NIT_SWITCH(nit_, e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbq, (const void*)ln_mod_bwd_kernel<(NIT < 0 ? -NIT : NIT), T, T, G>, 256, 0))
       if (dout_dtype == MMDIT_BF16) { if (gated) { LNQ(bf16_t, true); } else { LNQ(bf16_t, false); } }
       else if (dout_dtype == MMDIT_F32) { if (gated) { LNQ(float, true); } else { LNQ(float, false); } }
 #undef LNQ
@@ -1258,15 +1157,28 @@ extern "C" int mmdit_ln_modulate_bwd_pair(const mmdit_ln_bwd_problem* a, const m
     per_cu = per_cu < occ[dev][ni][ti][gi] ? per_cu : occ[dev][ni][ti][gi];
   }
   const long slots = (long)cus * per_cu;
-  int rch = LN_BWD_RCH;
   if (wgs(LN_BWD_RCH) > slots && wgs(LN_BWD_RCH) <= 2 * slots)
     for (int r = LN_BWD_RCH + 4; r <= 64; r += 4)
-      if (wgs(r) <= slots) { rch = r; break; }
-  for (int i = 0; i < 2; i++) {
-    const mmdit_ln_bwd_problem* p = src[i];
+      if (wgs(r) <= slots) return r;
+  return LN_BWD_RCH;
+}
+
+extern "C" int mmdit_ln_modulate_bwd(const mmdit_ln_bwd_problem* probs, int count, int d, int dout_dtype, mmdit_stream_t stream) {
+  MMDIT_CHECK_ARG(probs && count >= 1 && count <= 2 && d > 0 && d % 4 == 0 && d <= 4096);
+  const bool gated = probs[0].acc != nullptr;
+  for (int i = 0; i < count; i++) {
+    const mmdit_ln_bwd_problem* p = probs + i;
+    MMDIT_CHECK_ARG((p->acc != nullptr) == gated);
     MMDIT_CHECK_ARG(p->dout && p->x && p->mean && p->rstd && p->scale && p->dx && p->dscale && p->dshift && p->rows > 0 && p->rows_per_batch > 0 &&
                     p->rows % p->rows_per_batch == 0 && p->ld_mod % 4 == 0);
     if (gated) MMDIT_CHECK_ARG(p->gate && p->dacc && p->dgate && p->ld_gate % 4 == 0);
+  }
+  if (dout_dtype != MMDIT_BF16 && dout_dtype != MMDIT_F32) return MMDIT_ERR_DTYPE;
+  const int rch = count == 2 ? ln_bwd_one_round_rch(probs, probs + 1, d, dout_dtype, gated) : LN_BWD_RCH;
+  LnBwdProb q[2] = {};
+  int nb[2] = {0, 0};
+  for (int i = 0; i < count; i++) {
+    const mmdit_ln_bwd_problem* p = probs + i;
     const int nchunk = (p->rows_per_batch + rch - 1) / rch;
     nb[i] = (p->rows / p->rows_per_batch) * nchunk;
     q[i] = LnBwdProb{p->dout, p->x, p->mean, p->rstd, p->scale, p->ld_mod, p->dres, p->rows_per_batch, nchunk, p->dx, p->dscale, p->dshift, p->ld_dmod,
@@ -1276,11 +1188,10 @@ extern "C" int mmdit_ln_modulate_bwd_pair(const mmdit_ln_bwd_problem* a, const m
   const int nit = nit_for(d);
   dim3 grid(nb[0] + nb[1]);
 // (the backward keeps its range checks: without them the batched loads cost 24 more VGPRs = one wave per SIMD less, measured 79 -> 84 us)
-#define LNP(T, G) NIT_SWITCH(nit, hipLaunchKernelGGL((ln_mod_bwd_pair_kernel<(NIT < 0 ? -NIT : NIT), T, T, G>), grid, dim3(256), 0, s, q[0], q[1], nb[0], d, rch))
-  if (dout_dtype == MMDIT_BF16) { if (gated) { LNP(bf16_t, true); } else { LNP(bf16_t, false); } }
-  else if (dout_dtype == MMDIT_F32) { if (gated) { LNP(float, true); } else { LNP(float, false); } }
-  else return MMDIT_ERR_DTYPE;
-#undef LNP
+#define LNL(T, G) NIT_SWITCH(nit, hipLaunchKernelGGL((ln_mod_bwd_kernel<(NIT < 0 ? -NIT : NIT), T, T, G>), grid, dim3(256), 0, s, q[0], q[1], nb[0], d, rch))
+  if (dout_dtype == MMDIT_BF16) { if (gated) { LNL(bf16_t, true); } else { LNL(bf16_t, false); } }
+  else { if (gated) { LNL(float, true); } else { LNL(float, false); } }
+#undef LNL
   return mmdit_launch_status();
 }
 
@@ -1328,22 +1239,6 @@ extern "C" int mmdit_text_rmsnorm_bwd(const void* dout1, const void* dout2, int 
   return mmdit_launch_status();
 }
 
-extern "C" int mmdit_qk_norm_rope_fwd(const void* qkv, int qkv_dtype, const float* wq, const float* wk, const float* rope_cos, const float* rope_sin,
-                                      int batch, int tokens, int heads, int s_total, int tok0, void* Q, void* K, void* V, mmdit_stream_t stream) {
-  MMDIT_CHECK_ARG(qkv && wq && wk && Q && K && V && batch > 0 && tokens > 0 && heads > 0 && tok0 >= 0 && tok0 + tokens <= s_total);
-  MMDIT_CHECK_ARG((rope_cos == nullptr) == (rope_sin == nullptr));
-  hipStream_t s = (hipStream_t)stream;
-  MMDIT_CHECK_ARG(24 * heads <= 1024);   // one row per workgroup of 24*heads threads
-  const int rows = batch * tokens;
-  int g = rows < 1024 ? rows : 1024;
-  if (rope_cos && tokens <= 1024 && rows >= tokens) g = (g / tokens > 0 ? g / tokens : 1) * tokens;
-  dim3 grid(g);
-  if (qkv_dtype == MMDIT_BF16) hipLaunchKernelGGL((qk_norm_rope_fwd_kernel<bf16_t>), grid, dim3(24 * heads), 0, s, (const bf16_t*)qkv, wq, wk, rope_cos, rope_sin, rows, tokens, heads, s_total, tok0, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V);
-  else if (qkv_dtype == MMDIT_F32) hipLaunchKernelGGL((qk_norm_rope_fwd_kernel<float>), grid, dim3(24 * heads), 0, s, (const float*)qkv, wq, wk, rope_cos, rope_sin, rows, tokens, heads, s_total, tok0, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V);
-  else return MMDIT_ERR_DTYPE;
-  return mmdit_launch_status();
-}
-
 // Launch shape of the QK-norm/RoPE backward: RL row lanes per workgroup (as many as fit 1024 threads; every workgroup ends with 128
 // global atomics on the same two cache lines, so fewer, fatter workgroups), `lanes` rows in flight per iteration pair, a multiple of the
 // tokens per sample when RoPE applies (same token for all rows of a lane: factors loaded once).
@@ -1369,125 +1264,108 @@ static int qk_bwd_grid(int rows, int tokens, bool rope, int& rl) {
   return k * tokens / rl;
 }
 
-extern "C" int mmdit_qk_norm_rope_bwd(const void* dQ, const void* dK, const void* dV, int dq_dtype, const void* qkv, int qkv_dtype,
-                                      const float* wq, const float* wk, const float* rope_cos, const float* rope_sin,
-                                      int batch, int tokens, int heads, int s_total, int tok0, void* dqkv, int dqkv_dtype, float* dwq, float* dwk, mmdit_stream_t stream) {
-  MMDIT_CHECK_ARG(dQ && dK && dV && qkv && wq && wk && dqkv && dwq && dwk && batch > 0 && tokens > 0 && heads > 0 && tok0 >= 0 && tok0 + tokens <= s_total);
-  MMDIT_CHECK_ARG((rope_cos == nullptr) == (rope_sin == nullptr));
-  hipStream_t s = (hipStream_t)stream;
-  MMDIT_CHECK_ARG(heads >= 1 && 24 * heads <= 1024);   // one row per workgroup of 24*heads threads
-  const int rows = batch * tokens;
-  int rl = qk_bwd_rl(heads, rows);
-  dim3 grid(qk_bwd_grid(rows, tokens, rope_cos != nullptr, rl));
-  const bool fast = !rope_cos || ((int)grid.x * rl) % tokens == 0;
-#define QKB(TG, TI, TO) do { if (fast) hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<true, TG, TI, TO>), grid, dim3(24 * heads * rl), 0, s, (const TG*)dQ, (const TG*)dK, (const TG*)dV, (const TI*)qkv, wq, wk, rope_cos, rope_sin, rows, tokens, heads, s_total, tok0, (TO*)dqkv, dwq, dwk); \
-  else hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<false, TG, TI, TO>), grid, dim3(24 * heads * rl), 0, s, (const TG*)dQ, (const TG*)dK, (const TG*)dV, (const TI*)qkv, wq, wk, rope_cos, rope_sin, rows, tokens, heads, s_total, tok0, (TO*)dqkv, dwq, dwk); } while (0)
-  if (dq_dtype == MMDIT_BF16 && qkv_dtype == MMDIT_BF16 && dqkv_dtype == MMDIT_BF16) QKB(bf16_t, bf16_t, bf16_t);
-  else if (dq_dtype == MMDIT_F32 && qkv_dtype == MMDIT_F32 && dqkv_dtype == MMDIT_F32) QKB(float, float, float);
-  else if (dq_dtype == MMDIT_BF16 && qkv_dtype == MMDIT_F32 && dqkv_dtype == MMDIT_F32) QKB(bf16_t, float, float);
-  else return MMDIT_ERR_DTYPE;
-#undef QKB
-  return mmdit_launch_status();
-}
-
-extern "C" int mmdit_qk_norm_rope_fwd_pair(const mmdit_qk_problem* a, const mmdit_qk_problem* b, int qkv_dtype, int batch, int heads, int s_total,
-                                           void* Q, void* K, void* V, mmdit_stream_t stream) {
-  MMDIT_CHECK_ARG(a && b && Q && K && V && batch > 0 && heads > 0 && 24 * heads <= 1024);
-  const mmdit_qk_problem* src[2] = {a, b};
-  QkProb q[2];
-  int g[2];
-  for (int i = 0; i < 2; i++) {
-    const mmdit_qk_problem* p = src[i];
-    MMDIT_CHECK_ARG(p->qkv && p->wq && p->wk && p->tokens > 0 && p->tok0 >= 0 && p->tok0 + p->tokens <= s_total && (p->rope_cos == nullptr) == (p->rope_sin == nullptr));
-    const int rows = batch * p->tokens;
-    g[i] = rows < 1024 ? rows : 1024;
-    if (p->rope_cos && p->tokens <= 1024) g[i] = (g[i] / p->tokens > 0 ? g[i] / p->tokens : 1) * p->tokens;
-    q[i] = QkProb{p->qkv, p->wq, p->wk, p->rope_cos, p->rope_sin, rows, p->tokens, p->tok0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  }
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid(g[0] + g[1]);
-  if (qkv_dtype == MMDIT_BF16) hipLaunchKernelGGL((qk_norm_rope_fwd_pair_kernel<bf16_t>), grid, dim3(24 * heads), 0, s, q[0], q[1], g[0], heads, s_total, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V);
-  else if (qkv_dtype == MMDIT_F32) hipLaunchKernelGGL((qk_norm_rope_fwd_pair_kernel<float>), grid, dim3(24 * heads), 0, s, q[0], q[1], g[0], heads, s_total, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V);
-  else return MMDIT_ERR_DTYPE;
-  return mmdit_launch_status();
-}
-
-extern "C" int mmdit_qk_norm_rope_bwd_pair(const mmdit_qk_problem* a, const mmdit_qk_problem* b, const void* dQ, const void* dK, const void* dV, int dq_dtype,
-                                           int qkv_dtype, int dqkv_dtype, int batch, int heads, int s_total, mmdit_stream_t stream) {
-  MMDIT_CHECK_ARG(a && b && dQ && dK && dV && batch > 0 && heads > 0 && 24 * heads <= 1024);
-  const mmdit_qk_problem* src[2] = {a, b};
-  QkProb q[2];
-  int g[2];
-  for (int i = 0; i < 2; i++) {
-    const mmdit_qk_problem* p = src[i];
-    MMDIT_CHECK_ARG(p->qkv && p->wq && p->wk && p->dqkv && p->dwq && p->dwk && p->tokens > 0 && p->tok0 >= 0 && p->tok0 + p->tokens <= s_total &&
-                    (p->rope_cos == nullptr) == (p->rope_sin == nullptr));
-    q[i] = QkProb{p->qkv, p->wq, p->wk, p->rope_cos, p->rope_sin, batch * p->tokens, p->tokens, p->tok0, dQ, dK, dV, p->dqkv, p->dwq, p->dwk};
-  }
-  int rl = qk_bwd_rl(heads, q[0].rows < q[1].rows ? q[0].rows : q[1].rows);     // (one block shape for both problems)
-  for (int i = 0; i < 2; i++) g[i] = qk_bwd_grid(q[i].rows, q[i].tokens, q[i].rcos != nullptr, rl);
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid(g[0] + g[1]);
-  bool fast = true;
-  for (int i = 0; i < 2; i++) fast = fast && (!q[i].rcos || (g[i] * rl) % q[i].tokens == 0);
-#define QKP(TG, TI, TO) do { if (fast) hipLaunchKernelGGL((qk_norm_rope_bwd_pair_kernel<true, TG, TI, TO>), grid, dim3(24 * heads * rl), 0, s, q[0], q[1], g[0], heads, s_total); \
-  else hipLaunchKernelGGL((qk_norm_rope_bwd_pair_kernel<false, TG, TI, TO>), grid, dim3(24 * heads * rl), 0, s, q[0], q[1], g[0], heads, s_total); } while (0)
-  if (dq_dtype == MMDIT_BF16 && qkv_dtype == MMDIT_BF16 && dqkv_dtype == MMDIT_BF16) QKP(bf16_t, bf16_t, bf16_t);
-  else if (dq_dtype == MMDIT_F32 && qkv_dtype == MMDIT_F32 && dqkv_dtype == MMDIT_F32) QKP(float, float, float);
-  else if (dq_dtype == MMDIT_BF16 && qkv_dtype == MMDIT_F32 && dqkv_dtype == MMDIT_F32) QKP(bf16_t, float, float);
-  else return MMDIT_ERR_DTYPE;
-#undef QKP
-  return mmdit_launch_status();
-}
-
-// kv_merge_attn (Attention.py:243-251): see qk_merge_fwd_body.  K / V: (batch, heads, s_total / 2, 64); Q and dQ as in the plain pair launches.
-static int qk_merge_check(const mmdit_qk_problem* p, int s_total, bool bwd) {
+// pointers and token range of one QK-norm + RoPE problem (bwd: its gradient pointers too)
+static int qk_check(const mmdit_qk_problem* p, int s_total, bool bwd) {
   if (!(p->qkv && p->wq && p->wk && p->tokens > 0 && p->tok0 >= 0 && p->tok0 + p->tokens <= s_total && (p->rope_cos == nullptr) == (p->rope_sin == nullptr))) return MMDIT_ERR_ARG;
   if (bwd && !(p->dqkv && p->dwq && p->dwk)) return MMDIT_ERR_ARG;
-  if ((p->tokens | p->tok0 | s_total) & 1) return MMDIT_ERR_SHAPE;      // a pair never straddles two streams or two samples
   return 0;
 }
-extern "C" int mmdit_qk_norm_rope_fwd_merge_pair(const mmdit_qk_problem* a, const mmdit_qk_problem* b, int qkv_dtype, int batch, int heads, int s_total,
-                                                 void* Q, void* K, void* V, mmdit_stream_t stream) {
-  MMDIT_CHECK_ARG(a && b && Q && K && V && batch > 0 && heads > 0 && 24 * heads <= 512);      // one pair per workgroup of 24 * heads threads; the kernels are bounded at 512 (255 VGPRs: both rows of a pair and their factors stay in registers)
+// kv_merge_attn averages adjacent token pairs, and a pair never straddles two streams or two samples: an odd tokens, tok0 or s_total is MMDIT_ERR_SHAPE
+static int qk_merge_check(const mmdit_qk_problem* p, int s_total, bool bwd) {
+  if (int e = qk_check(p, s_total, bwd)) return e;
+  if ((p->tokens | p->tok0 | s_total) & 1) return MMDIT_ERR_SHAPE;
+  return 0;
+}
+// The four QK-norm + RoPE launchers (plain and kv_merge, forward and backward) validate their list here, once, and get the kernel-side problems
+// back.  max_threads: 1024, or 512 for the merge kernels (255 VGPRs: both rows of a pair and their factors stay in registers) -- a workgroup
+// is one row (one pair) of 24 * heads threads.  bwd: dQ / dK / dV and the per-problem gradient pointers are required.  merge: qk_merge_check.
+static int qk_list(const mmdit_qk_problem* probs, int count, int batch, int heads, int s_total, int max_threads, bool merge,
+                   bool bwd, const void* dQ, const void* dK, const void* dV, QkProb (&q)[2]) {
+  MMDIT_CHECK_ARG(probs && count >= 1 && count <= 2 && batch > 0 && heads > 0 && 24 * heads <= max_threads && (!bwd || (dQ && dK && dV)));
+  for (int i = 0; i < count; i++) {
+    const mmdit_qk_problem* p = probs + i;
+    if (int e = merge ? qk_merge_check(p, s_total, bwd) : qk_check(p, s_total, bwd)) return e;
+    q[i] = QkProb{p->qkv, p->wq, p->wk, p->rope_cos, p->rope_sin, batch * p->tokens, p->tokens, p->tok0, dQ, dK, dV,
+                  bwd ? p->dqkv : nullptr, bwd ? p->dwq : nullptr, bwd ? p->dwk : nullptr};
+  }
+  return 0;
+}
+// dtype combinations of the backward kernels (dQ / dK / dV, saved qkv, dqkv): 0 all bf16, 1 all fp32, 2 bf16 gradients of an fp32 projection
+static int qk_bwd_combo(int dq_dtype, int qkv_dtype, int dqkv_dtype) {
+  return (dq_dtype == MMDIT_BF16 && qkv_dtype == MMDIT_BF16 && dqkv_dtype == MMDIT_BF16) ? 0
+       : (dq_dtype == MMDIT_F32 && qkv_dtype == MMDIT_F32 && dqkv_dtype == MMDIT_F32)    ? 1
+       : (dq_dtype == MMDIT_BF16 && qkv_dtype == MMDIT_F32 && dqkv_dtype == MMDIT_F32)   ? 2 : -1;
+}
+
+extern "C" int mmdit_qk_norm_rope_fwd(const mmdit_qk_problem* probs, int count, int qkv_dtype, int batch, int heads, int s_total,
+                                      void* Q, void* K, void* V, mmdit_stream_t stream) {
+  MMDIT_CHECK_ARG(Q && K && V);
+  QkProb q[2] = {};
+  if (int e = qk_list(probs, count, batch, heads, s_total, 1024, false, false, nullptr, nullptr, nullptr, q)) return e;
   if (qkv_dtype != MMDIT_BF16 && qkv_dtype != MMDIT_F32) return MMDIT_ERR_DTYPE;
-  const mmdit_qk_problem* src[2] = {a, b};
-  QkProb q[2];
-  int g[2];
-  for (int i = 0; i < 2; i++) {
-    const mmdit_qk_problem* p = src[i];
-    if (int e = qk_merge_check(p, s_total, false)) return e;
-    const int pairs = batch * (p->tokens / 2);
-    g[i] = pairs < 1024 ? pairs : 1024;
-    q[i] = QkProb{p->qkv, p->wq, p->wk, p->rope_cos, p->rope_sin, batch * p->tokens, p->tokens, p->tok0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  int g[2] = {0, 0};
+  for (int i = 0; i < count; i++) {
+    g[i] = q[i].rows < 1024 ? q[i].rows : 1024;
+    if (q[i].rcos && q[i].tokens <= 1024 && q[i].rows >= q[i].tokens) g[i] = (g[i] / q[i].tokens > 0 ? g[i] / q[i].tokens : 1) * q[i].tokens;
   }
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(g[0] + g[1]);
-  if (qkv_dtype == MMDIT_BF16) hipLaunchKernelGGL((qk_merge_fwd_pair_kernel<bf16_t>), grid, dim3(24 * heads), 0, s, q[0], q[1], g[0], heads, s_total, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V);
-  else hipLaunchKernelGGL((qk_merge_fwd_pair_kernel<float>), grid, dim3(24 * heads), 0, s, q[0], q[1], g[0], heads, s_total, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V);
+  if (qkv_dtype == MMDIT_BF16) hipLaunchKernelGGL((qk_norm_rope_fwd_kernel<bf16_t>), grid, dim3(24 * heads), 0, s, q[0], q[1], g[0], heads, s_total, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V);
+  else hipLaunchKernelGGL((qk_norm_rope_fwd_kernel<float>), grid, dim3(24 * heads), 0, s, q[0], q[1], g[0], heads, s_total, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V);
   return mmdit_launch_status();
 }
 
-extern "C" int mmdit_qk_norm_rope_bwd_merge_pair(const mmdit_qk_problem* a, const mmdit_qk_problem* b, const void* dQ, const void* dK, const void* dV, int dq_dtype,
-                                                 int qkv_dtype, int dqkv_dtype, int batch, int heads, int s_total, mmdit_stream_t stream) {
-  MMDIT_CHECK_ARG(a && b && dQ && dK && dV && batch > 0 && heads > 0 && 24 * heads <= 512);
-  const int combo = (dq_dtype == MMDIT_BF16 && qkv_dtype == MMDIT_BF16 && dqkv_dtype == MMDIT_BF16) ? 0
-                  : (dq_dtype == MMDIT_F32 && qkv_dtype == MMDIT_F32 && dqkv_dtype == MMDIT_F32)    ? 1
-                  : (dq_dtype == MMDIT_BF16 && qkv_dtype == MMDIT_F32 && dqkv_dtype == MMDIT_F32)   ? 2 : -1;
+extern "C" int mmdit_qk_norm_rope_bwd(const mmdit_qk_problem* probs, int count, const void* dQ, const void* dK, const void* dV, int dq_dtype,
+                                      int qkv_dtype, int dqkv_dtype, int batch, int heads, int s_total, mmdit_stream_t stream) {
+  QkProb q[2] = {};
+  if (int e = qk_list(probs, count, batch, heads, s_total, 1024, false, true, dQ, dK, dV, q)) return e;
+  const int combo = qk_bwd_combo(dq_dtype, qkv_dtype, dqkv_dtype);
   if (combo < 0) return MMDIT_ERR_DTYPE;
-  const mmdit_qk_problem* src[2] = {a, b};
-  QkProb q[2];
-  int g[2];
-  for (int i = 0; i < 2; i++) {
-    const mmdit_qk_problem* p = src[i];
-    if (int e = qk_merge_check(p, s_total, true)) return e;
-    const int pairs = batch * (p->tokens / 2);
-    g[i] = pairs < 512 ? pairs : 512;      // (every workgroup ends with 128 global atomics on the same two cache lines: a small grid)
-    q[i] = QkProb{p->qkv, p->wq, p->wk, p->rope_cos, p->rope_sin, batch * p->tokens, p->tokens, p->tok0, dQ, dK, dV, p->dqkv, p->dwq, p->dwk};
+  int rl = qk_bwd_rl(heads, count == 2 && q[1].rows < q[0].rows ? q[1].rows : q[0].rows);     // (one block shape for every problem of the list)
+  int g[2] = {0, 0};
+  bool fast = true;
+  for (int i = 0; i < count; i++) {
+    g[i] = qk_bwd_grid(q[i].rows, q[i].tokens, q[i].rcos != nullptr, rl);
+    fast = fast && (!q[i].rcos || (g[i] * rl) % q[i].tokens == 0);
   }
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(g[0] + g[1]);
-#define QKM(TG, TI, TO) hipLaunchKernelGGL((qk_merge_bwd_pair_kernel<TG, TI, TO>), grid, dim3(24 * heads), 0, s, q[0], q[1], g[0], heads, s_total)
+#define QKL(TG, TI, TO) do { if (fast) hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<true, TG, TI, TO>), grid, dim3(24 * heads * rl), 0, s, q[0], q[1], g[0], heads, s_total); \
+  else hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<false, TG, TI, TO>), grid, dim3(24 * heads * rl), 0, s, q[0], q[1], g[0], heads, s_total); } while (0)
+  if (combo == 0) QKL(bf16_t, bf16_t, bf16_t);
+  else if (combo == 1) QKL(float, float, float);
+  else QKL(bf16_t, float, float);
+#undef QKL
+  return mmdit_launch_status();
+}
+
+// kv_merge_attn (Attention.py:243-251): see qk_merge_fwd_body.  K / V: (batch, heads, s_total / 2, 64); Q and dQ as in the plain launches.
+extern "C" int mmdit_qk_norm_rope_fwd_merge(const mmdit_qk_problem* probs, int count, int qkv_dtype, int batch, int heads, int s_total,
+                                            void* Q, void* K, void* V, mmdit_stream_t stream) {
+  MMDIT_CHECK_ARG(Q && K && V);
+  QkProb q[2] = {};
+  if (int e = qk_list(probs, count, batch, heads, s_total, 512, true, false, nullptr, nullptr, nullptr, q)) return e;
+  if (qkv_dtype != MMDIT_BF16 && qkv_dtype != MMDIT_F32) return MMDIT_ERR_DTYPE;
+  int g[2] = {0, 0};
+  for (int i = 0; i < count; i++) { const int pairs = q[i].rows / 2; g[i] = pairs < 1024 ? pairs : 1024; }
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid(g[0] + g[1]);
+  if (qkv_dtype == MMDIT_BF16) hipLaunchKernelGGL((qk_merge_fwd_kernel<bf16_t>), grid, dim3(24 * heads), 0, s, q[0], q[1], g[0], heads, s_total, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V);
+  else hipLaunchKernelGGL((qk_merge_fwd_kernel<float>), grid, dim3(24 * heads), 0, s, q[0], q[1], g[0], heads, s_total, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V);
+  return mmdit_launch_status();
+}
+
+extern "C" int mmdit_qk_norm_rope_bwd_merge(const mmdit_qk_problem* probs, int count, const void* dQ, const void* dK, const void* dV, int dq_dtype,
+                                            int qkv_dtype, int dqkv_dtype, int batch, int heads, int s_total, mmdit_stream_t stream) {
+  QkProb q[2] = {};
+  if (int e = qk_list(probs, count, batch, heads, s_total, 512, true, true, dQ, dK, dV, q)) return e;
+  const int combo = qk_bwd_combo(dq_dtype, qkv_dtype, dqkv_dtype);
+  if (combo < 0) return MMDIT_ERR_DTYPE;
+  int g[2] = {0, 0};
+  for (int i = 0; i < count; i++) { const int pairs = q[i].rows / 2; g[i] = pairs < 512 ? pairs : 512; }      // (every workgroup ends with 128 global atomics on the same two cache lines: a small grid)
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid(g[0] + g[1]);
+#define QKM(TG, TI, TO) hipLaunchKernelGGL((qk_merge_bwd_kernel<TG, TI, TO>), grid, dim3(24 * heads), 0, s, q[0], q[1], g[0], heads, s_total)
   if (combo == 0) QKM(bf16_t, bf16_t, bf16_t);
   else if (combo == 1) QKM(float, float, float);
   else QKM(bf16_t, float, float);
@@ -1495,23 +1373,22 @@ extern "C" int mmdit_qk_norm_rope_bwd_merge_pair(const mmdit_qk_problem* a, cons
   return mmdit_launch_status();
 }
 
-extern "C" int mmdit_mlp_act_bwd_pair(const mmdit_mlp_bwd_problem* a, const mmdit_mlp_bwd_problem* b, int dtype, int hidden, int gelu, mmdit_stream_t stream) {
-  MMDIT_CHECK_ARG(a && b && hidden > 0 && hidden % 8 == 0);
-  const mmdit_mlp_bwd_problem* src[2] = {a, b};
-  MlpBwdProb q[2];
-  int nby[2];
-  for (int i = 0; i < 2; i++) {
-    MMDIT_CHECK_ARG(src[i]->dh && src[i]->gu && src[i]->dgu && src[i]->rows > 0);
-    q[i] = MlpBwdProb{src[i]->dh, src[i]->gu, src[i]->dgu, src[i]->rows, src[i]->dbias};
-    nby[i] = (src[i]->rows + MB_RCH - 1) / MB_RCH;
+extern "C" int mmdit_mlp_act_bwd(const mmdit_mlp_bwd_problem* probs, int count, int dtype, int hidden, int gelu, mmdit_stream_t stream) {
+  MMDIT_CHECK_ARG(probs && count >= 1 && count <= 2 && hidden > 0 && hidden % 8 == 0);
+  MlpBwdProb q[2] = {};
+  int nby[2] = {0, 0};
+  for (int i = 0; i < count; i++) {
+    MMDIT_CHECK_ARG(probs[i].dh && probs[i].gu && probs[i].dgu && probs[i].rows > 0);
+    q[i] = MlpBwdProb{probs[i].dh, probs[i].gu, probs[i].dgu, probs[i].rows, probs[i].dbias};
+    nby[i] = (probs[i].rows + MB_RCH - 1) / MB_RCH;
   }
   dim3 grid((hidden + 255) / 256, nby[0] + nby[1]);
   hipStream_t s = (hipStream_t)stream;
-#define MBP(T, G) hipLaunchKernelGGL((mlp_act_bwd_pair_kernel<T, G>), grid, dim3(256), 0, s, q[0], q[1], nby[0], hidden)
-  if (dtype == MMDIT_BF16) { if (gelu) MBP(bf16_t, true); else MBP(bf16_t, false); }
-  else if (dtype == MMDIT_F32) { if (gelu) MBP(float, true); else MBP(float, false); }
+#define MBL(T, G) hipLaunchKernelGGL((mlp_act_bwd_kernel<T, G>), grid, dim3(256), 0, s, q[0], q[1], nby[0], hidden)
+  if (dtype == MMDIT_BF16) { if (gelu) MBL(bf16_t, true); else MBL(bf16_t, false); }
+  else if (dtype == MMDIT_F32) { if (gelu) MBL(float, true); else MBL(float, false); }
   else return MMDIT_ERR_DTYPE;
-#undef MBP
+#undef MBL
   return mmdit_launch_status();
 }
 
@@ -1525,16 +1402,6 @@ static int mlp_act_fwd(const void* gu, void* h, int dtype, int rows, int hidden,
   else return MMDIT_ERR_DTYPE;
   return mmdit_launch_status();
 }
-template <bool GELU>
-static int mlp_act_bwd(const void* dh, const void* gu, void* dgu, int dtype, int rows, int hidden, float* dbias, mmdit_stream_t stream) {
-  MMDIT_CHECK_ARG(dh && gu && dgu && rows > 0 && hidden > 0 && hidden % 8 == 0);
-  dim3 grid((hidden + 255) / 256, (rows + MB_RCH - 1) / MB_RCH);
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == MMDIT_BF16) hipLaunchKernelGGL((mlp_act_bwd_kernel<bf16_t, GELU>), grid, dim3(256), 0, s, (const bf16_t*)dh, (const bf16_t*)gu, (bf16_t*)dgu, rows, hidden, dbias);
-  else if (dtype == MMDIT_F32) hipLaunchKernelGGL((mlp_act_bwd_kernel<float, GELU>), grid, dim3(256), 0, s, (const float*)dh, (const float*)gu, (float*)dgu, rows, hidden, dbias);
-  else return MMDIT_ERR_DTYPE;
-  return mmdit_launch_status();
-}
 extern "C" int mmdit_swiglu_fwd_mx(const void* gu, int dtype, int rows, int hidden, void* q_fp8, void* scales_e8m0, mmdit_stream_t stream) {
   MMDIT_CHECK_ARG(gu && q_fp8 && scales_e8m0 && rows > 0 && hidden > 0 && hidden % 64 == 0);
   dim3 grid((hidden + 255) / 256, (rows + CO_RCH - 1) / CO_RCH);
@@ -1544,9 +1411,7 @@ extern "C" int mmdit_swiglu_fwd_mx(const void* gu, int dtype, int rows, int hidd
   return mmdit_launch_status();
 }
 extern "C" int mmdit_swiglu_fwd(const void* gu, void* h, int dtype, int rows, int hidden, mmdit_stream_t st) { return mlp_act_fwd<false>(gu, h, dtype, rows, hidden, st); }
-extern "C" int mmdit_swiglu_bwd(const void* dh, const void* gu, void* dgu, int dtype, int rows, int hidden, float* dbias, mmdit_stream_t st) { return mlp_act_bwd<false>(dh, gu, dgu, dtype, rows, hidden, dbias, st); }
 extern "C" int mmdit_gelu_fwd(const void* u, void* h, int dtype, int rows, int hidden, mmdit_stream_t st) { return mlp_act_fwd<true>(u, h, dtype, rows, hidden, st); }
-extern "C" int mmdit_gelu_bwd(const void* dh, const void* u, void* du, int dtype, int rows, int hidden, float* dbias, mmdit_stream_t st) { return mlp_act_bwd<true>(dh, u, du, dtype, rows, hidden, dbias, st); }
 
 extern "C" int mmdit_silu_bwd(const void* dy, int dy_dtype, const float* pre, void* dpre, int dpre_dtype, int rows, int cols, float* dbias, int rows_per_bias,
                               mmdit_stream_t stream) {

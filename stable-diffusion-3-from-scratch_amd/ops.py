@@ -467,66 +467,59 @@ def cast_multi(pairs):
     check(_lib.lib().mmdit_cast_multi(_p(t["dev"][0]), _p(t["dev"][1]), _p(t["dev"][2]), t["n"], _s()), "mmdit_cast_multi")
 
 
-def ln_modulate_fwd(x, scale, shift, rows_per_batch, out_dtype):
-    rows, d = x.shape
-    out = torch.empty((rows, d), dtype=out_dtype, device=x.device)
-    mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
-    rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
-    check(_lib.lib().mmdit_ln_modulate_fwd(_p(_c(x)), _p(scale), _p(shift), scale.stride(0), rows, d, rows_per_batch,
-                                           _p(out), _dt(out), _p(mean), _p(rstd), _s()), "mmdit_ln_modulate_fwd")
-    return out, mean, rstd
-
-
-def ln_modulate_fwd_res(x, acc, gate, scale, shift, rows_per_batch, out_dtype):
-    """x1 = x + gate[b] * acc, then adaLN of x1: returns (x1 fp32, out, mean, rstd) -- mmdit_ln_modulate_fwd_res."""
-    rows, d = x.shape
-    x1 = torch.empty((rows, d), dtype=torch.float32, device=x.device)
-    out = torch.empty((rows, d), dtype=out_dtype, device=x.device)
-    mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
-    rstd = torch.empty((rows,), dtype=torch.float32, device=x.device)
-    check(_lib.lib().mmdit_ln_modulate_fwd_res(_p(_c(x)), _p(_c(acc)), _dt(acc), _p(gate), gate.stride(0), _p(x1), _p(scale), _p(shift), scale.stride(0),
-                                               rows, d, rows_per_batch, _p(out), _dt(out), _p(mean), _p(rstd), _s()), "mmdit_ln_modulate_fwd_res")
-    return x1, out, mean, rstd
-
-
-def ln_modulate_fwd_pair(pa, pb, out_dtype):
-    """Two adaLN forward problems of the same width in ONE launch (the image and the text stream of a block; mmdit_ln_modulate_fwd_pair).
-    pa / pb: dicts with x, scale, shift, rpb and -- both or neither -- acc, gate (the pending gated residual update, as in
-    ln_modulate_fwd_res).  Returns [(x1, out, mean, rstd), (x1, out, mean, rstd)] (x1 is x itself without acc)."""
-    res = pa.get("acc") is not None
-    assert (pb.get("acc") is not None) == res
-    d = pa["x"].shape[1]
-    probs, outs = (_lib.LnFwdProblem * 2)(), []
-    for q, p in zip(probs, (pa, pb)):
+def _ln_fwd(plist, out_dtype):
+    """adaLN forward of a list of 1 or 2 problems of the same width in ONE launch (mmdit_ln_modulate_fwd).  A problem is a dict with x, scale,
+    shift, rpb and -- in all problems or in none -- acc, gate (the pending gated residual update x1 = x + gate[b] * acc).
+    Returns [(x1, out, mean, rstd)] per problem (x1 is x itself without acc)."""
+    res = plist[0].get("acc") is not None
+    d = plist[0]["x"].shape[1]
+    probs, outs, keep = (_lib.LnFwdProblem * len(plist))(), [], []
+    for q, p in zip(probs, plist):
+        assert (p.get("acc") is not None) == res
         x = _c(p["x"])
-        rows = x.shape[0]
-        dev = x.device
+        rows, dev = x.shape[0], x.device
         x1 = torch.empty((rows, d), dtype=torch.float32, device=dev) if res else x
         out = torch.empty((rows, d), dtype=out_dtype, device=dev)
         mean = torch.empty((rows,), dtype=torch.float32, device=dev)
         rstd = torch.empty((rows,), dtype=torch.float32, device=dev)
         q.x, q.scale, q.shift, q.ld_mod, q.rows, q.rows_per_batch = _p(x), _p(p["scale"]), _p(p["shift"]), p["scale"].stride(0), rows, p["rpb"]
         q.out, q.mean, q.rstd = _p(out), _p(mean), _p(rstd)
+        keep.append(x)
         if res:
             acc = _c(p["acc"])
             q.acc, q.gate, q.ld_gate, q.x_out = _p(acc), _p(p["gate"]), p["gate"].stride(0), _p(x1)
-            p["_keep"] = (x, acc)
-        else:
-            p["_keep"] = (x,)
+            keep.append(acc)
         outs.append((x1, out, mean, rstd))
-    acc_dt = _dt(pa["acc"]) if res else _DT[out_dtype]
-    check(_lib.lib().mmdit_ln_modulate_fwd_pair(ctypes.byref(probs[0]), ctypes.byref(probs[1]), d, acc_dt, _DT[out_dtype], _s()), "mmdit_ln_modulate_fwd_pair")
+    acc_dt = _dt(plist[0]["acc"]) if res else _DT[out_dtype]
+    check(_lib.lib().mmdit_ln_modulate_fwd(probs, len(plist), d, acc_dt, _DT[out_dtype], _s()), "mmdit_ln_modulate_fwd")
     return outs
 
 
-def ln_modulate_bwd_pair(pa, pb):
-    """Two adaLN backward problems in one launch (mmdit_ln_modulate_bwd_pair).  pa / pb: dicts with dout, x, mean, rstd, scale, dres (or
-    None), rpb, dscale, dshift and -- both or neither -- gated = (acc, gate, dgate, dbias | None).  Returns [dx or (dx, dacc)] * 2."""
-    gated = pa.get("gated") is not None
-    assert (pb.get("gated") is not None) == gated
-    d = pa["x"].shape[1]
-    probs, outs, keep = (_lib.LnBwdProblem * 2)(), [], []
-    for q, p in zip(probs, (pa, pb)):
+def ln_modulate_fwd(x, scale, shift, rows_per_batch, out_dtype):
+    return _ln_fwd([dict(x=x, scale=scale, shift=shift, rpb=rows_per_batch)], out_dtype)[0][1:]
+
+
+def ln_modulate_fwd_res(x, acc, gate, scale, shift, rows_per_batch, out_dtype):
+    """x1 = x + gate[b] * acc, then adaLN of x1: returns (x1 fp32, out, mean, rstd)."""
+    return _ln_fwd([dict(x=x, scale=scale, shift=shift, rpb=rows_per_batch, acc=acc, gate=gate)], out_dtype)[0]
+
+
+def ln_modulate_fwd_pair(pa, pb, out_dtype):
+    """Two adaLN forward problems of the same width in ONE launch (the image and the text stream of a block).  pa / pb: dicts as for
+    _ln_fwd.  Returns [(x1, out, mean, rstd), (x1, out, mean, rstd)]."""
+    return _ln_fwd([pa, pb], out_dtype)
+
+
+def _ln_bwd(plist):
+    """adaLN backward of a list of 1 or 2 problems in one launch (mmdit_ln_modulate_bwd).  A problem is a dict with dout, x, mean, rstd, scale,
+    dres (or None), rpb, dscale, dshift (views with the same leading dimension, accumulated into) and -- in all problems or in none --
+    gated = (acc, gate, dgate, dbias | None): also the backward of the gated residual update that consumes dx.
+    Returns dx (fp32), or (dx, dacc) with dacc = dx * gate in acc's dtype, per problem."""
+    gated = plist[0].get("gated") is not None
+    d = plist[0]["x"].shape[1]
+    probs, outs, keep = (_lib.LnBwdProblem * len(plist))(), [], []
+    for q, p in zip(probs, plist):
+        assert (p.get("gated") is not None) == gated
         dout, x = _c(p["dout"]), p["x"]
         rows, dev = x.shape[0], x.device
         dx = torch.empty((rows, d), dtype=torch.float32, device=dev)
@@ -537,6 +530,8 @@ def ln_modulate_bwd_pair(pa, pb):
         if gated:
             acc, gate, dgate, dbias = p["gated"]
             acc = _c(acc)
+            if acc.dtype != dout.dtype:
+                raise RuntimeError(f"ln_modulate_bwd: acc ({acc.dtype}) and dout ({dout.dtype}) must have one dtype")
             dacc = torch.empty((rows, d), dtype=acc.dtype, device=dev)
             q.acc, q.gate, q.ld_gate, q.dacc, q.dgate, q.ld_dgate = _p(acc), _p(gate), gate.stride(0), _p(dacc), _p(dgate), dgate.stride(0)
             q.dbias, q.ld_dbias = _p(dbias), (dbias.stride(0) if dbias is not None else 0)
@@ -544,8 +539,13 @@ def ln_modulate_bwd_pair(pa, pb):
             outs.append((dx, dacc))
         else:
             outs.append(dx)
-    check(_lib.lib().mmdit_ln_modulate_bwd_pair(ctypes.byref(probs[0]), ctypes.byref(probs[1]), d, _dt(pa["dout"]), _s()), "mmdit_ln_modulate_bwd_pair")
+    check(_lib.lib().mmdit_ln_modulate_bwd(probs, len(plist), d, _dt(plist[0]["dout"]), _s()), "mmdit_ln_modulate_bwd")
     return outs
+
+
+def ln_modulate_bwd_pair(pa, pb):
+    """Two adaLN backward problems in one launch.  pa / pb: dicts as for _ln_bwd.  Returns [dx or (dx, dacc)] * 2."""
+    return _ln_bwd([pa, pb])
 
 
 def gate_residual_fwd(x, acc, gate, rows_per_batch):
@@ -559,20 +559,11 @@ def gate_residual_fwd(x, acc, gate, rows_per_batch):
 def ln_modulate_bwd(dout, x, mean, rstd, scale, dres, rows_per_batch, dscale, dshift, gated=None):
     """Returns dx (fp32) = dres + LN-backward; accumulates into the dscale / dshift views (same leading dim).
     gated = (acc, gate, dgate, dbias | None): also run the backward of the gated residual update that consumes dx
-    (mmdit_ln_modulate_bwd_gated) and return (dx, dacc) with dacc = dx * gate in acc's dtype."""
-    rows, d = x.shape
-    dx = torch.empty((rows, d), dtype=torch.float32, device=x.device)
-    if gated is None:
-        check(_lib.lib().mmdit_ln_modulate_bwd(_p(_c(dout)), _dt(dout), _p(x), _p(mean), _p(rstd), _p(scale), scale.stride(0), _p(dres),
-                                               rows, d, rows_per_batch, _p(dx), _p(dscale), _p(dshift), dscale.stride(0), _s()), "mmdit_ln_modulate_bwd")
-        return dx
-    acc, gate, dgate, dbias = gated
-    dacc = torch.empty((rows, d), dtype=acc.dtype, device=x.device)
-    check(_lib.lib().mmdit_ln_modulate_bwd_gated(_p(_c(dout)), _dt(dout), _p(x), _p(mean), _p(rstd), _p(scale), scale.stride(0), _p(dres),
-                                                 rows, d, rows_per_batch, _p(dx), _p(dscale), _p(dshift), dscale.stride(0),
-                                                 _p(_c(acc)), _dt(acc), _p(gate), gate.stride(0), _p(dacc), _p(dgate), dgate.stride(0),
-                                                 _p(dbias), dbias.stride(0) if dbias is not None else 0, _s()), "mmdit_ln_modulate_bwd_gated")
-    return dx, dacc
+    and return (dx, dacc) with dacc = dx * gate in acc's dtype."""
+    p = dict(dout=dout, x=x, mean=mean, rstd=rstd, scale=scale, dres=dres, rpb=rows_per_batch, dscale=dscale, dshift=dshift)
+    if gated is not None:
+        p["gated"] = gated
+    return _ln_bwd([p])[0]
 
 
 def text_rmsnorm_fwd(x, w1, w2, s1, s2, split, out_dtype):
@@ -593,42 +584,45 @@ def text_rmsnorm_bwd(dout1, dout2, x, w1, w2, s1, s2, split):
     return dw1, dw2, ds1, ds2
 
 
+def _qk(fn, streams, batch, heads, s_total, T3, out_dtype=None, status=check):
+    """One launch of the QK-norm + RoPE entry point `fn` over a list of 1 or 2 streams = (qkv, wq, wk, rope_cos, rope_sin, tokens, tok0) and, for the
+    backward entry points (out_dtype given), + (dwq, dwk), which are ADDED to.  T3 = the joint (Q, K, V) written by a forward, the
+    (dQ, dK, dV) read by a backward; a backward returns [dqkv] per stream."""
+    probs, outs = (_lib.QkProblem * len(streams))(), []
+    for q, st in zip(probs, streams):
+        qkv, wq, wk, rc, rs, tokens, tok0 = st[:7]
+        q.qkv, q.wq, q.wk, q.rope_cos, q.rope_sin, q.tokens, q.tok0 = _p(_c(qkv)), _p(wq), _p(wk), _p(rc), _p(rs), tokens, tok0
+        if out_dtype is not None:
+            dqkv = torch.empty(qkv.shape, dtype=out_dtype, device=qkv.device)
+            q.dqkv, q.dwq, q.dwk = _p(dqkv), _p(st[7]), _p(st[8])
+            outs.append(dqkv)
+    a, b, c = (_p(t) for t in T3)
+    launch, qkv_dt = getattr(_lib.lib(), fn), _dt(streams[0][0])
+    if out_dtype is None:
+        status(launch(probs, len(streams), qkv_dt, batch, heads, s_total, a, b, c, _s()), fn)
+    else:
+        status(launch(probs, len(streams), a, b, c, _dt(T3[0]), qkv_dt, _DT[out_dtype], batch, heads, s_total, _s()), fn)
+    return outs
+
+
 def qk_norm_rope_fwd(qkv, wq, wk, rope_cos, rope_sin, batch, tokens, heads, s_total, tok0, Q, K, V):
-    check(_lib.lib().mmdit_qk_norm_rope_fwd(_p(_c(qkv)), _dt(qkv), _p(wq), _p(wk), _p(rope_cos), _p(rope_sin), batch, tokens, heads, s_total, tok0,
-                                            _p(Q), _p(K), _p(V), _s()), "mmdit_qk_norm_rope_fwd")
+    _qk("mmdit_qk_norm_rope_fwd", [(qkv, wq, wk, rope_cos, rope_sin, tokens, tok0)], batch, heads, s_total, (Q, K, V))
 
 
 def qk_norm_rope_bwd(dQ, dK, dV, qkv, wq, wk, rope_cos, rope_sin, batch, tokens, heads, s_total, tok0, dwq, dwk, out_dtype):
-    dqkv = torch.empty(qkv.shape, dtype=out_dtype, device=qkv.device)
-    check(_lib.lib().mmdit_qk_norm_rope_bwd(_p(dQ), _p(dK), _p(dV), _dt(dQ), _p(qkv), _dt(qkv), _p(wq), _p(wk), _p(rope_cos), _p(rope_sin),
-                                            batch, tokens, heads, s_total, tok0, _p(dqkv), _dt(dqkv), _p(dwq), _p(dwk), _s()), "mmdit_qk_norm_rope_bwd")
-    return dqkv
+    return _qk("mmdit_qk_norm_rope_bwd", [(qkv, wq, wk, rope_cos, rope_sin, tokens, tok0, dwq, dwk)], batch, heads, s_total, (dQ, dK, dV), out_dtype)[0]
 
 
 def qk_norm_rope_fwd_pair(img, txt, batch, heads, s_total, Q, K, V):
-    """The image and the text rows of a block in one launch (mmdit_qk_norm_rope_fwd_pair).  img / txt = (qkv, wq, wk, rope_cos, rope_sin,
-    tokens, tok0); both write the joint Q / K / V."""
-    probs, keep = (_lib.QkProblem * 2)(), []
-    for q, (qkv, wq, wk, rc, rs, tokens, tok0) in zip(probs, (img, txt)):
-        qkv = _c(qkv)
-        keep.append(qkv)
-        q.qkv, q.wq, q.wk, q.rope_cos, q.rope_sin, q.tokens, q.tok0 = _p(qkv), _p(wq), _p(wk), _p(rc), _p(rs), tokens, tok0
-    check(_lib.lib().mmdit_qk_norm_rope_fwd_pair(ctypes.byref(probs[0]), ctypes.byref(probs[1]), _dt(img[0]), batch, heads, s_total, _p(Q), _p(K), _p(V), _s()),
-          "mmdit_qk_norm_rope_fwd_pair")
+    """The image and the text rows of a block in one launch.  img / txt = (qkv, wq, wk, rope_cos, rope_sin, tokens, tok0); both write the
+    joint Q / K / V."""
+    _qk("mmdit_qk_norm_rope_fwd", [img, txt], batch, heads, s_total, (Q, K, V))
 
 
 def qk_norm_rope_bwd_pair(dQ, dK, dV, img, txt, batch, heads, s_total, out_dtype):
-    """Backward of both streams in one launch (mmdit_qk_norm_rope_bwd_pair).  img / txt = (qkv, wq, wk, rope_cos, rope_sin, tokens, tok0, dwq, dwk);
+    """Backward of both streams in one launch.  img / txt = (qkv, wq, wk, rope_cos, rope_sin, tokens, tok0, dwq, dwk);
     returns (dqkv_img, dqkv_txt)."""
-    probs, outs = (_lib.QkProblem * 2)(), []
-    for q, (qkv, wq, wk, rc, rs, tokens, tok0, dwq, dwk) in zip(probs, (img, txt)):
-        dqkv = torch.empty(qkv.shape, dtype=out_dtype, device=qkv.device)
-        q.qkv, q.wq, q.wk, q.rope_cos, q.rope_sin, q.tokens, q.tok0 = _p(qkv), _p(wq), _p(wk), _p(rc), _p(rs), tokens, tok0
-        q.dqkv, q.dwq, q.dwk = _p(dqkv), _p(dwq), _p(dwk)
-        outs.append(dqkv)
-    check(_lib.lib().mmdit_qk_norm_rope_bwd_pair(ctypes.byref(probs[0]), ctypes.byref(probs[1]), _p(dQ), _p(dK), _p(dV), _dt(dQ), _dt(img[0]), _DT[out_dtype],
-                                                 batch, heads, s_total, _s()), "mmdit_qk_norm_rope_bwd_pair")
-    return outs
+    return _qk("mmdit_qk_norm_rope_bwd", [img, txt], batch, heads, s_total, (dQ, dK, dV), out_dtype)
 
 
 def _merge_status(status, what):
@@ -639,37 +633,23 @@ def _merge_status(status, what):
 
 def qk_norm_rope_fwd_merge_pair(img, txt, batch, heads, s_total, Q, K, V):
     """kv_merge_attn (Attention.py:243-251): qk_norm_rope_fwd_pair with the keys / values of adjacent token pairs averaged
-    (mmdit_qk_norm_rope_fwd_merge_pair).  img / txt = (qkv, wq, wk, rope_cos, rope_sin, tokens, tok0); Q is (batch, heads, s_total, 64),
+    (mmdit_qk_norm_rope_fwd_merge).  img / txt = (qkv, wq, wk, rope_cos, rope_sin, tokens, tok0); Q is (batch, heads, s_total, 64),
     K and V are (batch, heads, s_total / 2, 64), the pairs of a stream from row tok0 / 2."""
     for t, rows in ((Q, s_total), (K, s_total // 2), (V, s_total // 2)):
         if t.dtype != torch.bfloat16 or tuple(t.shape) != (batch, heads, rows, 64):
             raise RuntimeError(f"qk_norm_rope_fwd_merge_pair: Q / K / V are bfloat16 (batch, heads, {s_total} | {s_total // 2}, 64), got {t.dtype} {tuple(t.shape)}")
         _c(t)
-    probs, keep = (_lib.QkProblem * 2)(), []
-    for q, (qkv, wq, wk, rc, rs, tokens, tok0) in zip(probs, (img, txt)):
-        qkv = _c(qkv)
-        keep.append(qkv)
-        q.qkv, q.wq, q.wk, q.rope_cos, q.rope_sin, q.tokens, q.tok0 = _p(qkv), _p(wq), _p(wk), _p(rc), _p(rs), tokens, tok0
-    _merge_status(_lib.lib().mmdit_qk_norm_rope_fwd_merge_pair(ctypes.byref(probs[0]), ctypes.byref(probs[1]), _dt(img[0]), batch, heads, s_total,
-                                                                _p(Q), _p(K), _p(V), _s()), "mmdit_qk_norm_rope_fwd_merge_pair")
+    _qk("mmdit_qk_norm_rope_fwd_merge", [img, txt], batch, heads, s_total, (Q, K, V), status=_merge_status)
 
 
 def qk_norm_rope_bwd_merge_pair(dQ, dK, dV, img, txt, batch, heads, s_total, out_dtype):
-    """Backward of qk_norm_rope_fwd_merge_pair (mmdit_qk_norm_rope_bwd_merge_pair): dQ (batch, heads, s_total, 64), dK / dV (batch, heads,
+    """Backward of qk_norm_rope_fwd_merge_pair (mmdit_qk_norm_rope_bwd_merge): dQ (batch, heads, s_total, 64), dK / dV (batch, heads,
     s_total / 2, 64).  img / txt = (qkv, wq, wk, rope_cos, rope_sin, tokens, tok0, dwq, dwk); returns (dqkv_img, dqkv_txt), ADDS to dwq / dwk."""
     for t, rows in ((dQ, s_total), (dK, s_total // 2), (dV, s_total // 2)):
         if t.dtype != dQ.dtype or tuple(t.shape) != (batch, heads, rows, 64):
             raise RuntimeError(f"qk_norm_rope_bwd_merge_pair: dQ / dK / dV are (batch, heads, {s_total} | {s_total // 2}, 64) of one dtype, got {t.dtype} {tuple(t.shape)}")
         _c(t)
-    probs, outs = (_lib.QkProblem * 2)(), []
-    for q, (qkv, wq, wk, rc, rs, tokens, tok0, dwq, dwk) in zip(probs, (img, txt)):
-        dqkv = torch.empty(qkv.shape, dtype=out_dtype, device=qkv.device)
-        q.qkv, q.wq, q.wk, q.rope_cos, q.rope_sin, q.tokens, q.tok0 = _p(_c(qkv)), _p(wq), _p(wk), _p(rc), _p(rs), tokens, tok0
-        q.dqkv, q.dwq, q.dwk = _p(dqkv), _p(dwq), _p(dwk)
-        outs.append(dqkv)
-    _merge_status(_lib.lib().mmdit_qk_norm_rope_bwd_merge_pair(ctypes.byref(probs[0]), ctypes.byref(probs[1]), _p(dQ), _p(dK), _p(dV), _dt(dQ), _dt(img[0]),
-                                                                _DT[out_dtype], batch, heads, s_total, _s()), "mmdit_qk_norm_rope_bwd_merge_pair")
-    return outs
+    return _qk("mmdit_qk_norm_rope_bwd_merge", [img, txt], batch, heads, s_total, (dQ, dK, dV), out_dtype, status=_merge_status)
 
 
 def _kv_operands(Q, K, V, s_kv):
@@ -749,25 +729,27 @@ def mlp_act_fwd(gu, hidden, gelu=False):
     return h
 
 
-def mlp_act_bwd(dh, gu, hidden, dbias, gelu=False):
-    rows = gu.shape[0]
-    dgu = torch.empty_like(gu)
-    fn = _lib.lib().mmdit_gelu_bwd if gelu else _lib.lib().mmdit_swiglu_bwd
-    check(fn(_p(_c(dh)), _p(gu), _p(dgu), _dt(gu), rows, hidden, _p(dbias), _s()), "mmdit_mlp_act_bwd")
-    return dgu
-
-
-def mlp_act_bwd_pair(a, b, hidden, gelu=False):
-    """mlp_act_bwd of two problems of the same hidden width in one launch (mmdit_mlp_act_bwd_pair).  a / b = (dh, gu, dbias); returns [dgu, dgu]."""
-    probs, outs, keep = (_lib.MlpBwdProblem * 2)(), [], []
-    for q, (dh, gu, dbias) in zip(probs, (a, b)):
+def _mlp_bwd(plist, hidden, gelu):
+    """Activation backward of a list of 1 or 2 problems = (dh, gu, dbias | None) of the same hidden width in one launch (mmdit_mlp_act_bwd):
+    returns [dgu] per problem, ADDS the column sums of dgu to dbias."""
+    probs, outs, keep = (_lib.MlpBwdProblem * len(plist))(), [], []
+    for q, (dh, gu, dbias) in zip(probs, plist):
         dh = _c(dh)
         dgu = torch.empty_like(gu)
         q.dh, q.gu, q.dgu, q.rows, q.dbias = _p(dh), _p(gu), _p(dgu), gu.shape[0], _p(dbias)
         keep.append(dh)
         outs.append(dgu)
-    check(_lib.lib().mmdit_mlp_act_bwd_pair(ctypes.byref(probs[0]), ctypes.byref(probs[1]), _dt(a[1]), hidden, int(gelu), _s()), "mmdit_mlp_act_bwd_pair")
+    check(_lib.lib().mmdit_mlp_act_bwd(probs, len(plist), _dt(plist[0][1]), hidden, int(gelu), _s()), "mmdit_mlp_act_bwd")
     return outs
+
+
+def mlp_act_bwd(dh, gu, hidden, dbias, gelu=False):
+    return _mlp_bwd([(dh, gu, dbias)], hidden, gelu)[0]
+
+
+def mlp_act_bwd_pair(a, b, hidden, gelu=False):
+    """mlp_act_bwd of two problems of the same hidden width in one launch.  a / b = (dh, gu, dbias); returns [dgu, dgu]."""
+    return _mlp_bwd([a, b], hidden, gelu)
 
 
 def silu_bwd(dy, pre, out_dtype, dbias, rows_per_bias=0):

@@ -197,21 +197,24 @@ def test_qk_norm_rope(ops, dt, Bt, H, h2, w2, Mtxt):
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("Bt,H,h2,w2,Mtxt", [(2, 3, 4, 6, 10), (16, 12, 16, 16, 154), (16, 16, 32, 32, 154)])
-def test_qk_norm_rope_pair_launch_equals_two_launches(ops, dt, Bt, H, h2, w2, Mtxt):
-    """mmdit_qk_norm_rope_{fwd,bwd}_pair (image + text rows of a block in one launch) == the two single-stream launches: outputs
-    bit-identical, the atomically accumulated norm-weight gradients equal up to the order of the atomics."""
+@pytest.mark.parametrize("Bt,H,h2,w2,Mtxt,swap", [(2, 3, 4, 6, 10, False), (16, 12, 16, 16, 154, False), (16, 16, 32, 32, 154, False), (2, 3, 4, 6, 10, True)],
+                         ids=["2-3-4-6-10", "16-12-16-16-154", "16-16-32-32-154", "2-3-4-6-10-text-first"])
+def test_qk_norm_rope_pair_launch_equals_two_launches(ops, dt, Bt, H, h2, w2, Mtxt, swap):
+    """mmdit_qk_norm_rope_{fwd,bwd} on a list of two (image + text rows of a block in one launch) == two launches of a list of one: outputs
+    bit-identical, the atomically accumulated norm-weight gradients equal up to the order of the atomics.  swap: the same two problems with
+    the text stream first (problem 1's block offsets must agree with problem 0's whichever stream it is)."""
     N = h2 * w2
     S, d = N + Mtxt, H * 64
     cos, sin = _rope_tables(h2, w2)
     wqx, wkx, wqc, wkc = (1 + 0.1 * rnd(64, seed=i) for i in (1, 2, 3, 4))
     qkv_x, qkv_c = rnd(Bt * N, 3 * d, seed=5).to(dt), rnd(Bt * Mtxt, 3 * d, seed=6).to(dt)
+    order = (lambda a, b: (b, a)) if swap else (lambda a, b: (a, b))
     outs = []
     for pair in (False, True):
         Q = torch.zeros((Bt, H, S, 64), dtype=torch.bfloat16, device="cuda")
         K, V = torch.zeros_like(Q), torch.zeros_like(Q)
         if pair:
-            ops.qk_norm_rope_fwd_pair((qkv_x, wqx, wkx, cos, sin, N, 0), (qkv_c, wqc, wkc, None, None, Mtxt, N), Bt, H, S, Q, K, V)
+            ops.qk_norm_rope_fwd_pair(*order((qkv_x, wqx, wkx, cos, sin, N, 0), (qkv_c, wqc, wkc, None, None, Mtxt, N)), Bt, H, S, Q, K, V)
         else:
             ops.qk_norm_rope_fwd(qkv_x, wqx, wkx, cos, sin, Bt, N, H, S, 0, Q, K, V)
             ops.qk_norm_rope_fwd(qkv_c, wqc, wkc, None, None, Bt, Mtxt, H, S, N, Q, K, V)
@@ -223,7 +226,7 @@ def test_qk_norm_rope_pair_launch_equals_two_launches(ops, dt, Bt, H, h2, w2, Mt
     for pair in (False, True):
         dw = [torch.zeros(64, device="cuda") for _ in range(4)]
         if pair:
-            dx, dc = ops.qk_norm_rope_bwd_pair(dQ, dK, dV, (qkv_x, wqx, wkx, cos, sin, N, 0, dw[0], dw[1]), (qkv_c, wqc, wkc, None, None, Mtxt, N, dw[2], dw[3]), Bt, H, S, dt)
+            dx, dc = order(*ops.qk_norm_rope_bwd_pair(dQ, dK, dV, *order((qkv_x, wqx, wkx, cos, sin, N, 0, dw[0], dw[1]), (qkv_c, wqc, wkc, None, None, Mtxt, N, dw[2], dw[3])), Bt, H, S, dt))
         else:
             dx = ops.qk_norm_rope_bwd(dQ, dK, dV, qkv_x, wqx, wkx, cos, sin, Bt, N, H, S, 0, dw[0], dw[1], dt)
             dc = ops.qk_norm_rope_bwd(dQ, dK, dV, qkv_c, wqc, wkc, None, None, Bt, Mtxt, H, S, N, dw[2], dw[3], dt)
@@ -234,8 +237,9 @@ def test_qk_norm_rope_pair_launch_equals_two_launches(ops, dt, Bt, H, h2, w2, Mt
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("gelu", [False, True])
-def test_mlp_act_bwd_pair_launch_equals_two_launches(ops, dt, gelu):
+@pytest.mark.parametrize("gelu,swap", [(False, False), (True, False), (False, True), (True, True)], ids=["False", "True", "False-second-first", "True-second-first"])
+def test_mlp_act_bwd_pair_launch_equals_two_launches(ops, dt, gelu, swap):
+    """mmdit_mlp_act_bwd on a list of two == two launches of a list of one; swap: the same two problems in the other order."""
     hidden = 1536
     P = []
     for i, rows in enumerate((300, 77)):
@@ -243,7 +247,8 @@ def test_mlp_act_bwd_pair_launch_equals_two_launches(ops, dt, gelu):
     db1 = [torch.zeros(P[0][1].shape[1], device="cuda") for _ in P]
     single = [ops.mlp_act_bwd(dh, gu, hidden, db, gelu) for (dh, gu), db in zip(P, db1)]
     db2 = [torch.zeros(P[0][1].shape[1], device="cuda") for _ in P]
-    pair = ops.mlp_act_bwd_pair((P[0][0], P[0][1], db2[0]), (P[1][0], P[1][1], db2[1]), hidden, gelu)
+    order = (lambda a, b: (b, a)) if swap else (lambda a, b: (a, b))
+    pair = order(*ops.mlp_act_bwd_pair(*order((P[0][0], P[0][1], db2[0]), (P[1][0], P[1][1], db2[1])), hidden, gelu))
     for a, b in zip(single, pair):
         assert torch.equal(a, b)
     for a, b in zip(db1, db2):
@@ -275,7 +280,7 @@ def test_mlp_act(ops, dt, gelu):
 @pytest.mark.parametrize("d,rpb,Bt", [(768, 256, 3), (256, 154, 2), (1024, 77, 2)])
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 def test_ln_modulate_fwd_res_equals_residual_then_norm(ops, d, rpb, Bt, dt):
-    """mmdit_ln_modulate_fwd_res == (x + gate[b] * acc) followed by mmdit_ln_modulate_fwd, and both against torch fp32;
+    """mmdit_ln_modulate_fwd with acc == (x + gate[b] * acc) followed by the plain mmdit_ln_modulate_fwd, and both against torch fp32;
     mmdit_gate_residual_fwd is the update on its own."""
     rows = Bt * rpb
     x = rnd(rows, d, seed=1) * 2 + 0.5
@@ -294,7 +299,7 @@ def test_ln_modulate_fwd_res_equals_residual_then_norm(ops, d, rpb, Bt, dt):
 @pytest.mark.parametrize("d,rpb,Bt", [(768, 256, 3), (256, 154, 2), (1024, 77, 2)])
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 def test_ln_modulate_bwd_gated_equals_unfused_pair(ops, d, rpb, Bt, dt):
-    """mmdit_ln_modulate_bwd_gated == mmdit_ln_modulate_bwd followed by mmdit_gate_residual_bwd on its dx, to fp32 round-off (the
+    """mmdit_ln_modulate_bwd with acc (gated) == the plain mmdit_ln_modulate_bwd followed by mmdit_gate_residual_bwd on its dx, to fp32 round-off (the
     compiler contracts a*b+c differently in the two instantiations, so dx may differ in the last bit and dacc by one rounding of
     the activation dtype on a few elements); the atomically accumulated column sums likewise."""
     rows = Bt * rpb
@@ -489,7 +494,7 @@ def test_attention_fwd_bwd_at_the_1024px_stage_sequence_length(ops):
 @pytest.mark.parametrize("Bt,H,h2,w2,Mt,last", [(2, 3, 8, 8, 30, False), (1, 2, 16, 16, 154, False), (2, 2, 16, 16, 154, True), (1, 2, 32, 32, 154, False)])
 def test_attention_bwd_with_fused_qk_norm_rope_backward(ops, Bt, H, h2, w2, Mt, last):
     """mmdit_attn_bwd_qk (attention backward whose epilogues run the RoPE + QK-RMSNorm backward on the fp32 accumulators and write
-    the gradient of the raw QKV GEMM outputs) against (a) the two-pass composition mmdit_attn_bwd + mmdit_qk_norm_rope_bwd_pair and
+    the gradient of the raw QKV GEMM outputs) against (a) the two-pass composition mmdit_attn_bwd + mmdit_qk_norm_rope_bwd and
     (b) torch autograd through norm -> RoPE -> exact softmax attention on the same bf16 operands."""
     N = h2 * w2
     S, d = N + Mt, H * 64
@@ -623,7 +628,7 @@ def test_gemm_stream_k_grouped_wgrad(ops):
 def test_gemm_qkv_epilogue_with_qk_norm_rope_equals_gemm_plus_row_kernel(ops, Bt, H, h2, w2, Mt, K, claiming):
     """mmdit_gemm_qkv_norm_rope (QKV projection whose epilogue applies the per-head QK RMSNorm + axial RoPE and writes Q, K, V in the
     joint attention layout; Attention.py:118-135, 174-194, 258-261) against the two launches it replaces, mmdit_gemm_grouped +
-    mmdit_qk_norm_rope_fwd_pair: the q / k columns of the raw projections bit-identical, Q / K / V equal up to the last bf16 bit on a vanishing fraction of
+    mmdit_qk_norm_rope_fwd: the q / k columns of the raw projections bit-identical, Q / K / V equal up to the last bf16 bit on a vanishing fraction of
     the elements (the same arithmetic on the same rounded values; only instruction selection may differ), and both against an fp32
     torch reference.  MMDiT-B and MMDiT-L block shapes and a small ragged one (rows not a multiple of the tile, fewer than 32 tokens per sample).
     claiming: with mmdit_gemm_set_claiming(1) -- the data-parallel trainer's setting -- the planner gives the fused launch to the 8-phase kernel (epi8_qk:
@@ -679,7 +684,7 @@ def test_gemm_qkv_epilogue_with_qk_norm_rope_equals_gemm_plus_row_kernel(ops, Bt
 @pytest.mark.parametrize("Bt,H,h2,w2,Mt,K", [(16, 16, 32, 32, 154, 1024), (8, 12, 16, 16, 154, 768)])
 def test_gemm_qkv_epilogue_on_mx_operands_equals_gemm_plus_row_kernel(ops, Bt, H, h2, w2, Mt, K):
     """The same fusion on MX e4m3 operands (mxfp8 inference: the QKV projection of the 8-phase MX kernel with the QK-norm / RoPE epilogue) against
-    the MX GEMM followed by mmdit_qk_norm_rope_fwd_pair: raw q / k columns bit-identical, Q / K / V up to instruction selection."""
+    the MX GEMM followed by mmdit_qk_norm_rope_fwd: raw q / k columns bit-identical, Q / K / V up to instruction selection."""
     N = h2 * w2
     S, d = N + Mt, H * 64
     cos, sin = _rope_tables(h2, w2)
@@ -845,7 +850,7 @@ def test_gemm_wgrad_reduction_length_not_a_multiple_of_the_k_tile(ops):
 @pytest.mark.parametrize("M,h,K", [(16384, 3072, 768), (3000, 512, 128), (700, 264, 64)])
 def test_gemm_swiglu_bwd_epilogue_equals_gemm_plus_row_kernel(ops, M, h, K):
     """act=ACT_SWIGLU_BWD (the SwiGLU backward formed in the epilogue of the down-projection's data-gradient GEMM) must be BIT-identical
-    to the plain bf16 GEMM dh = dY W3 followed by mmdit_swiglu_bwd, the bias gradients equal up to the order of the fp32 atomics, and
+    to the plain bf16 GEMM dh = dY W3 followed by mmdit_mlp_act_bwd, the bias gradients equal up to the order of the fp32 atomics, and
     both agree with autograd through silu(g) * u -> F.linear (MLP.py:15-40) within bf16 rounding.  Ragged M and h, grouped launch."""
     probs, refs = [], []
     for s in range(2):
@@ -1117,17 +1122,19 @@ def _zero_mask_case(ops, workspace):
         assert all(torch.equal(a, b) for a, b in zip(*runs))
 
 
-@pytest.mark.parametrize("shape", [(4, 64, 39, 256), (64, 256, 154, 768), (16, 1024, 154, 1024)])
+@pytest.mark.parametrize("shape,swap", [((4, 64, 39, 256), False), ((64, 256, 154, 768), False), ((16, 1024, 154, 1024), False), ((4, 64, 39, 256), True)],
+                         ids=["shape0", "shape1", "shape2", "shape0-text-first"])
 @pytest.mark.parametrize("res", [False, True])
-def test_ln_modulate_pair_launch_equals_two_launches(ops, res, shape):
-    """mmdit_ln_modulate_fwd_pair / _bwd_pair (image + text stream of a block in one launch) are the single-problem kernels run on two
-    problems: outputs bit-identical, the atomically accumulated per-sample sums equal up to the order of the atomics.  The MMDiT-B batch-64
-    and MMDiT-L batch-16 shapes take the backward launcher's one-round sizing (28 rows per workgroup instead of 16)."""
+def test_ln_modulate_pair_launch_equals_two_launches(ops, res, shape, swap):
+    """mmdit_ln_modulate_fwd / _bwd on a list of two (image + text stream of a block in one launch) are the same kernels run on two lists
+    of one: outputs bit-identical, the atomically accumulated per-sample sums equal up to the order of the atomics.  The MMDiT-B batch-64
+    and MMDiT-L batch-16 shapes take the backward launcher's one-round sizing (28 rows per workgroup instead of 16).  swap: the same two
+    problems with the text stream first."""
     g = torch.Generator(device="cuda").manual_seed(11)
     B, N, Mt, d = shape
     rnd = lambda *s: torch.randn(s, generator=g, device="cuda")
     P = []
-    for rpb in (N, Mt):
+    for rpb in ((Mt, N) if swap else (N, Mt)):
         rows = B * rpb
         P.append(dict(x=rnd(rows, d) * 2, scale=rnd(B, d) * 0.3, shift=rnd(B, d) * 0.3, rpb=rpb, acc=rnd(rows, d).to(torch.bfloat16), gate=rnd(B, d),
                       dout=rnd(rows, d).to(torch.bfloat16), dres=rnd(rows, d)))
@@ -1162,6 +1169,80 @@ def test_ln_modulate_pair_launch_equals_two_launches(ops, res, shape):
             assert rel(ab[k], aa[k]) < 1e-5
         if res:
             assert rel(ab["gated"][2], aa["gated"][2]) < 1e-5 and rel(ab["gated"][3], aa["gated"][3]) < 1e-5
+
+
+def test_row_list_entry_points_reject_bad_lists(ops):
+    """The seven row-operation entry points that take a problem list accept count = 1 or 2 only: count 0 and count 3 are MMDIT_ERR_ARG, and so
+    is an adaLN list of two in which only one problem has acc.  NOTHING is launched: the sentinel-filled outputs stay untouched.  The same
+    valid problems (the smallest shapes of the *_pair_launch_equals_two_launches tests) are then accepted with count 1 and 2."""
+    from sd3_amd import _lib
+    L, st, BF = _lib.lib(), torch.cuda.current_stream().cuda_stream, torch.bfloat16
+    outs, keep = [], []
+
+    def sent(*shape, dtype=torch.float32):
+        outs.append(torch.full(shape, 7.0, dtype=dtype, device="cuda"))
+        return outs[-1].data_ptr()
+
+    def inp(*shape, dtype=torch.float32, seed=0):
+        keep.append(rnd(*shape, seed=seed, dtype=dtype))
+        return keep[-1]
+
+    # (a third, valid problem behind the two: a launcher that took count = 3 would read it and write to its sentinels)
+    B, d = 4, 256
+    lf, lb = (_lib.LnFwdProblem * 3)(), (_lib.LnBwdProblem * 3)()
+    for i, rpb in enumerate((64, 39, 64)):
+        rows = B * rpb
+        x, acc, dout, mod = inp(rows, d, seed=i), inp(rows, d, dtype=BF, seed=10 + i), inp(rows, d, dtype=BF, seed=20 + i), inp(B, 3 * d, seed=30 + i)
+        mean, rstd = inp(rows, seed=40 + i), inp(rows, seed=50 + i)
+        scale, shift, gate = (mod[:, k * d:].data_ptr() for k in range(3))
+        q = lf[i]
+        q.x, q.acc, q.gate, q.ld_gate, q.x_out = x.data_ptr(), acc.data_ptr(), gate, 3 * d, sent(rows, d)
+        q.scale, q.shift, q.ld_mod, q.rows, q.rows_per_batch = scale, shift, 3 * d, rows, rpb
+        q.out, q.mean, q.rstd = sent(rows, d, dtype=BF), sent(rows), sent(rows)
+        q = lb[i]
+        q.dout, q.x, q.mean, q.rstd, q.scale, q.ld_mod, q.rows, q.rows_per_batch = dout.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), scale, 3 * d, rows, rpb
+        q.dx, q.dscale, q.dshift, q.ld_dmod = sent(rows, d), sent(B, d), sent(B, d), d
+        q.acc, q.gate, q.ld_gate, q.dacc, q.dgate, q.ld_dgate, q.dbias, q.ld_dbias = acc.data_ptr(), gate, 3 * d, sent(rows, d, dtype=BF), sent(B, d), d, sent(B, d), d
+    Bt, H, N, Mt = 2, 3, 24, 10
+    S = N + Mt
+    cos, sin = _rope_tables(4, 6)
+    qk = (_lib.QkProblem * 3)()
+    for i, (tokens, tok0, rope) in enumerate(((N, 0, True), (Mt, N, False), (N, 0, True))):
+        q = qk[i]
+        q.qkv, q.wq, q.wk, q.tokens, q.tok0 = inp(Bt * tokens, 3 * H * 64, dtype=BF, seed=60 + i).data_ptr(), inp(64, seed=1).data_ptr(), inp(64, seed=2).data_ptr(), tokens, tok0
+        q.rope_cos, q.rope_sin = (cos.data_ptr(), sin.data_ptr()) if rope else (None, None)
+        q.dqkv, q.dwq, q.dwk = sent(Bt * tokens, 3 * H * 64, dtype=BF), sent(64), sent(64)
+    Q, K, V = (sent(Bt, H, S, 64, dtype=BF) for _ in range(3))
+    Km, Vm = (sent(Bt, H, S // 2, 64, dtype=BF) for _ in range(2))
+    dQ, dK, dV = (inp(Bt, H, S, 64, dtype=BF, seed=70 + i).data_ptr() for i in range(3))
+    hidden = 1536
+    ml = (_lib.MlpBwdProblem * 3)()
+    for i, rows in enumerate((300, 77, 300)):
+        q = ml[i]
+        q.dh, q.gu, q.dgu, q.rows, q.dbias = inp(rows, hidden, dtype=BF, seed=80 + i).data_ptr(), inp(rows, 2 * hidden, dtype=BF, seed=90 + i).data_ptr(), sent(rows, 2 * hidden, dtype=BF), rows, sent(2 * hidden)
+    b16 = _lib.BF16
+    calls = {
+        "mmdit_ln_modulate_fwd": lambda n: L.mmdit_ln_modulate_fwd(lf, n, d, b16, b16, st),
+        "mmdit_ln_modulate_bwd": lambda n: L.mmdit_ln_modulate_bwd(lb, n, d, b16, st),
+        "mmdit_qk_norm_rope_fwd": lambda n: L.mmdit_qk_norm_rope_fwd(qk, n, b16, Bt, H, S, Q, K, V, st),
+        "mmdit_qk_norm_rope_bwd": lambda n: L.mmdit_qk_norm_rope_bwd(qk, n, dQ, dK, dV, b16, b16, b16, Bt, H, S, st),
+        "mmdit_qk_norm_rope_fwd_merge": lambda n: L.mmdit_qk_norm_rope_fwd_merge(qk, n, b16, Bt, H, S, Q, Km, Vm, st),
+        "mmdit_qk_norm_rope_bwd_merge": lambda n: L.mmdit_qk_norm_rope_bwd_merge(qk, n, dQ, dK, dV, b16, b16, b16, Bt, H, S, st),
+        "mmdit_mlp_act_bwd": lambda n: L.mmdit_mlp_act_bwd(ml, n, b16, hidden, 0, st),
+    }
+    for name, call in calls.items():
+        assert call(0) == _lib.ERR_ARG and call(3) == _lib.ERR_ARG, name
+    for probs, name in ((lf, "mmdit_ln_modulate_fwd"), (lb, "mmdit_ln_modulate_bwd")):
+        for i in (0, 1):
+            acc, probs[i].acc = probs[i].acc, None
+            assert calls[name](2) == _lib.ERR_ARG, (name, i)
+            probs[i].acc = acc
+    torch.cuda.synchronize()
+    for t in outs:
+        assert bool((t == 7.0).all()), "a refused launch wrote to its outputs"
+    for name, call in calls.items():
+        assert call(1) == 0 and call(2) == 0, name
+    torch.cuda.synchronize()
 
 
 def _mx_reference(x):

@@ -1,7 +1,7 @@
 """kv_merge_attn (reference: Attention.py:243-251) at the ABI and construction level.  No GPU needed.
 
 The four entry points of the feature -- mmdit_attn_fwd_kv / mmdit_attn_bwd_kv (attention whose keys have a length of their own) and
-mmdit_qk_norm_rope_fwd_merge_pair / mmdit_qk_norm_rope_bwd_merge_pair (QK-norm + RoPE with adjacent keys / values averaged) -- are declared
+mmdit_qk_norm_rope_fwd_merge / mmdit_qk_norm_rope_bwd_merge (QK-norm + RoPE with adjacent keys / values averaged) -- are declared
 in include/mmdit_hip.h, bound with the prototypes' types and exported by the built library; the modules that used to raise for
 kv_merge_attn=True construct, with the state-dict keys and the params record of the reference; the options that stay out of scope keep
 raising."""
@@ -13,7 +13,7 @@ import re
 import pytest
 import torch
 
-NAMES = ["mmdit_attn_fwd_kv", "mmdit_attn_bwd_kv", "mmdit_qk_norm_rope_fwd_merge_pair", "mmdit_qk_norm_rope_bwd_merge_pair"]
+NAMES = ["mmdit_attn_fwd_kv", "mmdit_attn_bwd_kv", "mmdit_qk_norm_rope_fwd_merge", "mmdit_qk_norm_rope_bwd_merge"]
 MICRO = dict(dim=128, num_heads=2, num_blocks=3)
 
 
@@ -40,12 +40,12 @@ def test_declared_in_header():
     assert _prototype(txt, "mmdit_attn_bwd_kv") == ["const void* Q", "const void* K", "const void* V", "const void* Ox", "const void* Oc", "const void* dOx",
                                                     "const void* dOc", "const float* lse", "float* delta", "int batch", "int heads", "int S", "int s_kv", "int n_img",
                                                     "float scale", "void* dQ", "void* dK", "void* dV", "int dq_dtype", "mmdit_stream_t stream"]
-    assert _prototype(txt, "mmdit_qk_norm_rope_fwd_merge_pair") == _prototype(txt, "mmdit_qk_norm_rope_fwd_pair")
-    assert _prototype(txt, "mmdit_qk_norm_rope_bwd_merge_pair") == _prototype(txt, "mmdit_qk_norm_rope_bwd_pair")
+    assert _prototype(txt, "mmdit_qk_norm_rope_fwd_merge") == _prototype(txt, "mmdit_qk_norm_rope_fwd")
+    assert _prototype(txt, "mmdit_qk_norm_rope_bwd_merge") == _prototype(txt, "mmdit_qk_norm_rope_bwd")
     # every prototype of the header cites its call site in the reference
     assert txt.count("Attention.py:243-251") >= 2
-    # new symbols, no struct-layout or signature change: the version stays (mmdit_qk_problem is pinned by mmdit_struct_size)
-    assert "#define MMDIT_ABI_VERSION 9" in txt and L.ABI_VERSION == 9
+    # the version the row operations' list entry points came with (mmdit_qk_problem is pinned by mmdit_struct_size)
+    assert "#define MMDIT_ABI_VERSION 10" in txt and L.ABI_VERSION == 10
     # the plain entry points keep their signatures
     assert _prototype(txt, "mmdit_attn_fwd") == ["const void* Q", "const void* K", "const void* V", "int batch", "int heads", "int S", "int n_img",
                                                  "float scale", "int mode", "void* Ox", "void* Oc", "float* lse", "mmdit_stream_t stream"]
@@ -56,8 +56,8 @@ def test_bound_with_the_prototype_types():
     vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
     assert L._SIGNATURES["mmdit_attn_fwd_kv"] == ([vp, vp, vp, i, i, i, i, i, f, i, vp, vp, vp, vp], i)
     assert L._SIGNATURES["mmdit_attn_bwd_kv"] == ([vp] * 9 + [i, i, i, i, i, f, vp, vp, vp, i, vp], i)
-    assert L._SIGNATURES["mmdit_qk_norm_rope_fwd_merge_pair"] == L._SIGNATURES["mmdit_qk_norm_rope_fwd_pair"]
-    assert L._SIGNATURES["mmdit_qk_norm_rope_bwd_merge_pair"] == L._SIGNATURES["mmdit_qk_norm_rope_bwd_pair"]
+    assert L._SIGNATURES["mmdit_qk_norm_rope_fwd_merge"] == L._SIGNATURES["mmdit_qk_norm_rope_fwd"]
+    assert L._SIGNATURES["mmdit_qk_norm_rope_bwd_merge"] == L._SIGNATURES["mmdit_qk_norm_rope_bwd"]
 
 
 def test_exported_by_the_built_library():

@@ -1,7 +1,7 @@
 """kv_merge_attn on the GPU (reference: Attention.py:243-251): the keys and values of adjacent token pairs of each stream are averaged after
 the per-head RMSNorm and the axial RoPE, and S queries attend to S / 2 keys.
 
-  1, 2  mmdit_qk_norm_rope_fwd_merge_pair / _bwd_merge_pair         (csrc/rowops.hip)
+  1, 2  mmdit_qk_norm_rope_fwd_merge / _bwd_merge                   (csrc/rowops.hip)
   3     mmdit_attn_fwd_kv / mmdit_attn_bwd_kv at key-side tile edges (csrc/attention.hip, the KVL instantiations)
   4     ... bit-identical to mmdit_attn_fwd / mmdit_attn_bwd at s_kv == S
   5     the model against the reference's own golden (tests/golden/forward_micro_kvmerge.npz, tools/make_goldens_kvmerge.py), both routes
@@ -211,7 +211,6 @@ def test_merge_fwd(mcase, ops):
 @pytest.mark.parametrize("N,Mt", [(6, 3), (3, 4), (3, 3)], ids=["odd-text", "odd-image", "odd-both"])
 def test_merge_refuses_odd_token_counts(ops, N, Mt):
     """An odd tokens / tok0 / s_total: MMDIT_ERR_SHAPE from both entry points and NOTHING is launched (sentinel-filled outputs stay untouched)."""
-    import ctypes
     from sd3_amd import _lib
     Bt, H, S, d = 2, 3, N + Mt, 192
     cos, sin = _rope_tables(1, N)
@@ -228,9 +227,8 @@ def test_merge_refuses_odd_token_counts(ops, N, Mt):
         q.dqkv, q.dwq, q.dwk = dq.data_ptr(), dwq.data_ptr(), dwk.data_ptr()
     st = torch.cuda.current_stream().cuda_stream
     L = _lib.lib()
-    assert L.mmdit_qk_norm_rope_fwd_merge_pair(ctypes.byref(probs[0]), ctypes.byref(probs[1]), _lib.BF16, Bt, H, S, Q.data_ptr(), K.data_ptr(), V.data_ptr(), st) == _lib.ERR_SHAPE
-    assert L.mmdit_qk_norm_rope_bwd_merge_pair(ctypes.byref(probs[0]), ctypes.byref(probs[1]), Q.data_ptr(), K.data_ptr(), V.data_ptr(), _lib.BF16, _lib.BF16, _lib.BF16,
-                                               Bt, H, S, st) == _lib.ERR_SHAPE
+    assert L.mmdit_qk_norm_rope_fwd_merge(probs, 2, _lib.BF16, Bt, H, S, Q.data_ptr(), K.data_ptr(), V.data_ptr(), st) == _lib.ERR_SHAPE
+    assert L.mmdit_qk_norm_rope_bwd_merge(probs, 2, Q.data_ptr(), K.data_ptr(), V.data_ptr(), _lib.BF16, _lib.BF16, _lib.BF16, Bt, H, S, st) == _lib.ERR_SHAPE
     torch.cuda.synchronize()
     for t in [Q, K, V, dx, dc] + dw:
         assert bool((t == 7.0).all()), "a refused launch wrote to its outputs"

@@ -51,7 +51,7 @@ of = torch.cat([Ox[:nb].view(nb, N, H, hd), Oc[:nb].view(nb, M, H, hd)], 1).perm
 rel = lambda a, b: float((a - b).norm() / b.norm())
 print(f"rel err: O {rel(of, o.detach()):.2e}  dQ {rel(dQ[:nb].float(), q.grad):.2e}  dK {rel(dK[:nb].float(), k.grad):.2e}  dV {rel(dV[:nb].float(), v.grad):.2e}")
 
-# attention backward + QK-RMSNorm / RoPE backward: two passes (mmdit_attn_bwd + mmdit_qk_norm_rope_bwd_pair) vs the fused epilogues
+# attention backward + QK-RMSNorm / RoPE backward: two passes (mmdit_attn_bwd + mmdit_qk_norm_rope_bwd) vs the fused epilogues
 d = H * hd
 qkv_x, qkv_c = rnd(B * N, 3 * d), rnd(B * M, 3 * d)
 wts = [1 + 0.1 * torch.randn(64, generator=g, device="cuda") for _ in range(4)]

@@ -1,5 +1,5 @@
 """(round 4) The QKV projection of one MMDiT-B block at batch 64 (image 16384 + text 9856 rows, d = 768, 12 heads) with the QK-norm + RoPE +
-joint-layout store in its epilogue (mmdit_gemm_qkv_norm_rope), timed; against GEMM + mmdit_qk_norm_rope_fwd_pair.  With a probes build,
+joint-layout store in its epilogue (mmdit_gemm_qkv_norm_rope), timed; against GEMM + mmdit_qk_norm_rope_fwd.  With a probes build,
 MMDIT_GEMM_CFG=2 forces 256 x 256 tiles (the 8-phase kernel's QK epilogue) instead of the planner's 320 x 256 (the wide kernel).
 python tools/probes/qkv_fused_bench.py [reps]"""
 import os
