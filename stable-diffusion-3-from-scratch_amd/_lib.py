@@ -16,6 +16,7 @@ def experiment(name: str, default: str) -> str:
 
 LIB_PATH = os.environ.get("MMDIT_LIB") or os.path.join(_HERE, "libmmdit_hip.so")   # MMDIT_LIB: A/B a scratch build
 HEADER_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip.h")
+HEADER_EXT_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_ext.h")   # opt-in entry points outside the versioned core ABI
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_SILU, ACT_SWIGLU, ACT_SWIGLU_BWD = 0, 1, 2, 3
@@ -137,6 +138,11 @@ _SIGNATURES = {
     "mmdit_adamw_step_dlr": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, _d, _d, _d, _d, _vp], _i),
     "mmdit_cast_multi": ([_vp, _vp, _vp, _i, _vp], _i),
 }
+# entry points of include/mmdit_hip_ext.h: bound like the core table, not counted by MMDIT_ABI_VERSION
+_EXT_SIGNATURES = {
+    "mmdit_attn_fwd_e4m3": ([_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp], _i),
+}
+ATTN_E4M3_KEY_TILE, ATTN_E4M3_QUERY_TILE = 64, 128   # MMDIT_ATTN_E4M3_KEY_TILE / MMDIT_ATTN_E4M3_QUERY_TILE
 ADAMW_CHUNK = 65536   # MMDIT_ADAMW_CHUNK
 ABI_VERSION = 10      # MMDIT_ABI_VERSION of include/mmdit_hip.h this binding mirrors
 # struct ids of mmdit_struct_size() -> ctypes mirrors (None: laid out with numpy record dtypes in optim.py / ops.py: 48 / 24 bytes)
@@ -149,6 +155,13 @@ _lib = None
 def declared_symbols():
     """Entry points declared by include/mmdit_hip.h (parsed from the header text)."""
     with open(HEADER_PATH) as f:
+        txt = f.read()
+    return sorted(set(re.findall(r"\b(mmdit_[a-z0-9_]+)\s*\(", txt)) - {"mmdit_stream_t"})
+
+
+def declared_ext_symbols():
+    """Entry points declared by include/mmdit_hip_ext.h (parsed the same way)."""
+    with open(HEADER_EXT_PATH) as f:
         txt = f.read()
     return sorted(set(re.findall(r"\b(mmdit_[a-z0-9_]+)\s*\(", txt)) - {"mmdit_stream_t"})
 
@@ -170,7 +183,7 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        for name, (argtypes, restype) in _SIGNATURES.items():
+        for name, (argtypes, restype) in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError -> symbol missing: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

@@ -14,7 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmmdit_hip.so")
 HEADER = os.path.join(HERE, "..", "include", "mmdit_hip.h")
-SOURCES = ["gemm.hip", "gemm_dma.hip", "gemm_lean.hip", "gemm8p.hip", "gemm8p_inf.hip", "rowops.hip", "attention.hip", "vae.hip", "vae_attn.hip", "optim.hip"]
+HEADER_EXT = os.path.join(HERE, "..", "include", "mmdit_hip_ext.h")      # opt-in entry points outside the versioned core ABI
+SOURCES = ["gemm.hip", "gemm_dma.hip", "gemm_lean.hip", "gemm8p.hip", "gemm8p_inf.hip", "rowops.hip", "attention.hip", "attention_e4m3.hip", "vae.hip", "vae_attn.hip", "optim.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + os.environ.get("MMDIT_EXTRA_HIPCC_FLAGS", "").split()
 # per-source flags.  vae_attn.hip: its 128 output accumulators are rescaled by the VALU, so they must live in the VGPR half of the register
@@ -40,7 +41,7 @@ def _read(path):
 
 def source_hash(src):
     """Content hash of everything object `src` depends on."""
-    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [HEADER]
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [HEADER, HEADER_EXT]
     if src == "gemm8p_inf.hip":
         headers.append(os.path.join(CSRC, "gemm8p.hip"))      # (it is that file, compiled with MMDIT_G8_PART 2)
     return _sha([os.path.join(CSRC, src)] + headers, " ".join([HIPCC] + FLAGS + SOURCE_FLAGS.get(src, [])))

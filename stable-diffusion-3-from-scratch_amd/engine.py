@@ -40,6 +40,7 @@ class Mode:
         self.T = BF16 if fast else F32
         self.prec = PREC_BF16 if fast else PREC_SPLIT
         self.attn_mode = 0 if fast else 1
+        self.attn_e4m3 = False  # fp8 / mxfp8 only, opt-in (diff_model.set_precision(..., attention="e4m3")): e4m3 QK^T / PV attention (ops.attn_fwd_e4m3)
         self._q = {}            # id(packed bf16 weight) -> (weight, fp8 copy, scale); weights are static while sampling
 
     def act(self, t):
@@ -379,7 +380,12 @@ def block_fwd(m, w, X, C, y, dims, rope, cond=None, keep=True, lazy=False):
         ops.qk_norm_rope_fwd(sv.qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], B, N, H, S, 0, sv.Q, sv.K, sv.V)
         ops.qk_norm_rope_fwd(sv.qkv_c, w.wq_c, w.wk_c, None, None, B, Mt, H, S, N, sv.Q, sv.K, sv.V)
     if mxf:
-        sv.Oxa, sv.Oca = ops.attn_fwd_mx(sv.Q, sv.K, sv.V, N, 64 ** -0.5)
+        sv.Oxa, sv.Oca = ops.attn_fwd_e4m3(sv.Q, sv.K, sv.V, N, 64 ** -0.5, mx=True) if m.attn_e4m3 else ops.attn_fwd_mx(sv.Q, sv.K, sv.V, N, 64 ** -0.5)
+    elif m.fp8 and m.attn_e4m3 and not keep and not merge and dev.type == "cuda":      # (inference: no lse)
+        sv.Ox, sv.Oc = ops.attn_fwd_e4m3(sv.Q, sv.K, sv.V, N, 64 ** -0.5)
+        sv.Oxa = sv.Ox.view(B * N, d)
+        if both:
+            sv.Oca = sv.Oc.view(B * Mt, d)
     else:
         sv.Ox, sv.Oc, sv.lse = ops.attn_fwd(sv.Q, sv.K, sv.V, N, 64 ** -0.5, m.attn_mode, s_kv=S // 2 if merge else None)
         sv.Oxa = m.act(sv.Ox.view(B * N, d))

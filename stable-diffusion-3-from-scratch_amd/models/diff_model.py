@@ -147,17 +147,30 @@ class diff_model(nn.Module):
                          Wmod_out=Pack([self.out_norm.c_shift.weight, self.out_norm.c_scale.weight]), Wout=Pack([self.out_proj.weight]))
 
     # ------------------------------------------------------------------------------------------
-    def _mode(self):
-        return {"fast": engine.FAST, "parity": engine.PARITY, "fp8": engine.FP8, "mxfp8": engine.MXFP8}[self.precision]
+    @staticmethod
+    def _mode_of(precision):
+        return {"fast": engine.FAST, "parity": engine.PARITY, "fp8": engine.FP8, "mxfp8": engine.MXFP8}[precision]
 
-    def set_precision(self, precision: str):
+    def _mode(self):
+        return self._mode_of(self.precision)
+
+    def set_precision(self, precision: str, attention: str = "bf16"):
         """"fast" (bf16, training and inference), "parity" (fp32-exact GEMMs, the 1e-3 golden check) or "fp8": inference
-        only -- e4m3 operands with per-tensor scales for the QKV / out / MLP GEMMs of every block (BASELINE config 5)."""
+        only -- e4m3 operands with per-tensor scales for the QKV / out / MLP GEMMs of every block (BASELINE config 5).
+        attention="e4m3" ("fp8" / "mxfp8" only, opt-in): the attention between those GEMMs takes e4m3 operands as well
+        (ops.attn_fwd_e4m3: Q, K, V quantised inside the kernel); the default "bf16" keeps the bf16-MFMA flash kernels."""
         assert precision in ("fast", "parity", "fp8", "mxfp8")
         if precision in ("fp8", "mxfp8") and self.kv_merge_attn:
             raise RuntimeError(f"set_precision('{precision}'): kv_merge_attn has no e4m3 path (mmdit_attn_fwd_mx keeps one sequence length); use 'fast' or 'parity'")
+        if attention not in ("bf16", "e4m3"):
+            raise ValueError(f"set_precision: attention must be 'bf16' or 'e4m3', got {attention!r}")
+        if attention == "e4m3" and precision not in ("fp8", "mxfp8"):
+            raise ValueError(f"set_precision('{precision}', attention='e4m3'): e4m3 attention belongs to the 'fp8' / 'mxfp8' inference modes")
         engine.FP8._q.clear()
         engine.MXFP8._q.clear()
+        engine.FP8.attn_e4m3 = engine.MXFP8.attn_e4m3 = False
+        if attention == "e4m3":
+            self._mode_of(precision).attn_e4m3 = True
         for mod in self.modules():
             if hasattr(mod, "precision"):
                 mod.precision = "fast" if precision in ("fp8", "mxfp8") else precision     # stand-alone sub-modules have no fp8 path

@@ -407,6 +407,33 @@ def attn_fwd_mx(Q, K, V, n_img, scale):
     return MxAct(qx, sx), (MxAct(qc, scc) if n_txt else None)
 
 
+def attn_fwd_e4m3(Q, K, V, n_img, scale, mx=False):
+    """Flash attention forward with e4m3 operands on both matrix products (mmdit_attn_fwd_e4m3, include/mmdit_hip_ext.h; inference, no lse).
+    Q, K, V: bf16 (B, H, S, 64), quantised inside the launch.  Returns the head-merged (Ox (B, N, H*64), Oc (B, M, H*64) or None) in bf16, or
+    with mx=True what attn_fwd_mx returns: (MxAct (B*N, H*64), MxAct (B*M, H*64) or None)."""
+    B, H, S, hd = Q.shape
+    if hd != 64:
+        raise RuntimeError("attention kernels are built for head_dim 64 (the reference's dim = 64*num_heads convention)")
+    if K.shape != Q.shape or V.shape != Q.shape:
+        raise RuntimeError(f"attn_fwd_e4m3: K and V must have Q's shape {tuple(Q.shape)}, got {tuple(K.shape)} / {tuple(V.shape)}")
+    for t in (Q, K, V):
+        if t.dtype != torch.bfloat16:
+            raise RuntimeError("attention operands are bfloat16")
+        _c(t)
+    n_txt, D = S - n_img, H * hd
+    if S < 1 or not 0 <= n_img <= S:
+        check(_lib.ERR_SHAPE, "mmdit_attn_fwd_e4m3")       # (the library's own answer, before a buffer of negative size is asked for)
+    if mx:
+        qx, sx = _mx_buffers(B * n_img, D, Q.device)
+        qc, scc = _mx_buffers(B * n_txt, D, Q.device) if n_txt else (None, None)
+        check(_lib.lib().mmdit_attn_fwd_e4m3(_p(Q), _p(K), _p(V), B, H, S, n_img, float(scale), _p(qx), _p(qc), _p(sx), _p(scc), _s()), "mmdit_attn_fwd_e4m3")
+        return MxAct(qx, sx), (MxAct(qc, scc) if n_txt else None)
+    Ox = torch.empty((B, n_img, D), dtype=torch.bfloat16, device=Q.device)
+    Oc = torch.empty((B, n_txt, D), dtype=torch.bfloat16, device=Q.device) if n_txt else None
+    check(_lib.lib().mmdit_attn_fwd_e4m3(_p(Q), _p(K), _p(V), B, H, S, n_img, float(scale), _p(Ox), _p(Oc), None, None, _s()), "mmdit_attn_fwd_e4m3")
+    return Ox, Oc
+
+
 def quant_mxfp8(x):
     """MX (OCP microscaling) e4m3 quantisation of a row-major 2-D operand: returns (q: float8_e4m3fn like x, scales: uint8 E8M0 block
     scales in the GEMM's layout, see mx_scales_to_rows; 512 spare bytes behind them) -- mmdit_mxfp8_quantize; pass scale_mode=1 to gemm()."""

@@ -1,6 +1,9 @@
 """Attention micro-benchmark on the MMDiT-B shape (batch 64, 12 heads, 256 image + 154 text tokens, head_dim 64) or `reps B H N M`.
 Times forward and backward (prep + dQ + dK/dV launches) with HIP events; checks the outputs against a torch fp32 reference.
-python tools/attn_bench.py [reps]"""
+python tools/attn_bench.py [reps]
+python tools/attn_bench.py --e4m3 [--out=FILE] [reps [B H N M]]: the forward of the e4m3 inference modes instead -- mmdit_attn_fwd_e4m3 (bf16 and MX
+outputs) beside mmdit_attn_fwd mode 0 and mmdit_attn_fwd_mx, by default at the sampler's MMDiT-L shape (batch 16, 16 heads, 1024 image + 154 text
+tokens); the kernels alternate inside every round, the table gives median and min / max over the rounds and is appended to FILE."""
 import os
 import sys
 
@@ -10,8 +13,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sd3_amd  # noqa: E402,F401
 from sd3_amd import ops  # noqa: E402
 
+E4M3 = "--e4m3" in sys.argv
+OUT = next((a.split("=", 1)[1] for a in sys.argv if a.startswith("--out=")), None)
+sys.argv = [a for a in sys.argv if not a.startswith("--")]
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-B, H, N, M, hd = 64, 12, 256, 154, 64
+B, H, N, M, hd = (16, 16, 1024, 154, 64) if E4M3 else (64, 12, 256, 154, 64)
 if len(sys.argv) > 5:      # python tools/attn_bench.py reps B H N M   (e.g. 20 16 16 1024 154: MMDiT-L 512^2 batch 16)
     B, H, N, M = (int(v) for v in sys.argv[2:6])
 S = N + M
@@ -34,6 +40,42 @@ def timed(fn):
     torch.cuda.synchronize()
     return out, e0.elapsed_time(e1) / reps * 1e-3
 
+
+def e4m3_table(rounds=7):
+    """Forward kernels of the e4m3 inference modes, alternating inside each round (same inputs, same box, same minute)."""
+    import platform
+    import statistics
+    import time
+    kernels = [("mmdit_attn_fwd mode 0 (bf16 MFMA, bf16 out)", lambda: ops.attn_fwd(Q, K, V, N, scale, 0)),
+               ("mmdit_attn_fwd_mx (bf16 MFMA, MX out)", lambda: ops.attn_fwd_mx(Q, K, V, N, scale)),
+               ("mmdit_attn_fwd_e4m3 (e4m3 MFMA, bf16 out)", lambda: ops.attn_fwd_e4m3(Q, K, V, N, scale)),
+               ("mmdit_attn_fwd_e4m3 (e4m3 MFMA, MX out)", lambda: ops.attn_fwd_e4m3(Q, K, V, N, scale, mx=True))]
+    t = {name: [] for name, _ in kernels}
+    for _ in range(rounds):
+        for name, fn in kernels:
+            t[name].append(timed(fn)[1] * 1e6)
+    fl = 4.0 * B * H * S * S * hd
+    lines = [f"{time.strftime('%Y-%m-%d %H:%M')}  {torch.cuda.get_device_name(0)} ({platform.node()})  attention forward, B={B} H={H} S={S} (n_img={N}) head 64, "
+             f"{rounds} rounds x {reps} launches per kernel, HIP events; the two existing kernels are the parent commit's (csrc/attention.hip is unchanged)",
+             f"{'kernel':<46} {'median us':>10} {'min':>8} {'max':>8} {'TF (median)':>12}"]
+    for name, _ in kernels:
+        med = statistics.median(t[name])
+        lines.append(f"{name:<46} {med:10.1f} {min(t[name]):8.1f} {max(t[name]):8.1f} {fl / med / 1e6:12.1f}")
+    # accuracy on a slice of the batch: relative L2 against fp32 attention of the bf16 inputs
+    nb = min(B, 2)
+    ref = torch.softmax(Q[:nb].float() @ K[:nb].float().transpose(-1, -2) * scale, dim=-1) @ V[:nb].float()
+    cat = lambda ox, oc: torch.cat([ox[:nb].view(nb, N, H, hd), oc[:nb].view(nb, M, H, hd)], 1).permute(0, 2, 1, 3).float()
+    o0, o8 = cat(*ops.attn_fwd(Q, K, V, N, scale, 0)[:2]), cat(*ops.attn_fwd_e4m3(Q, K, V, N, scale))
+    lines.append(f"rel-L2 of O against fp32 attention: bf16 kernel {float((o0 - ref).norm() / ref.norm()):.2e}, e4m3 kernel {float((o8 - ref).norm() / ref.norm()):.2e}")
+    print("\n".join(lines))
+    if OUT:
+        with open(OUT, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if E4M3:
+    e4m3_table()
+    sys.exit(0)
 
 (Ox, Oc, lse), tf = timed(lambda: ops.attn_fwd(Q, K, V, N, scale, 0))
 (dQ, dK, dV), tb = timed(lambda: ops.attn_bwd(Q, K, V, Ox, Oc, dOx, dOc, lse, N, scale, torch.bfloat16))
