@@ -149,18 +149,6 @@ __device__ __forceinline__ void acc_to_lds(const f32x16 (&acc)[2], float* tile, 
       *LDS_PTR(f32x4, p + db * 32 + 8 * g) = (f32x4){acc[db][g * 4], acc[db][g * 4 + 1], acc[db][g * 4 + 2], acc[db][g * 4 + 3]};
   __builtin_amdgcn_wave_barrier();
 }
-// rows 16 half .. 16 half + 15 of the accumulator tile only, parked as rows 0 .. 15 of `tile16` (16 x QK_ROW_F floats)
-__device__ __forceinline__ void acc_to_lds_half(const f32x16 (&acc)[2], float* tile16, int lane, int half) {
-  if (((lane & 31) >> 4) == half) {
-    float* p = tile16 + (lane & 15) * QK_ROW_F + 4 * (lane >> 5);
-#pragma unroll
-    for (int db = 0; db < 2; db++)
-#pragma unroll
-      for (int g = 0; g < 4; g++)
-        *LDS_PTR(f32x4, p + db * 32 + 8 * g) = (f32x4){acc[db][g * 4], acc[db][g * 4 + 1], acc[db][g * 4 + 2], acc[db][g * 4 + 3]};
-  }
-  __builtin_amdgcn_wave_barrier();
-}
 __device__ __forceinline__ void lds_row8(const float* tile, int r, int c, float (&v)[8]) {
   const f32x4 a = *LDS_PTR(const f32x4, tile + r * QK_ROW_F + 8 * c), b = *LDS_PTR(const f32x4, tile + r * QK_ROW_F + 8 * c + 4);
 #pragma unroll
@@ -176,7 +164,6 @@ __device__ __forceinline__ void qk_bwd_rows(u32x4 (&xr)[4], int lane, int nvalid
 #pragma unroll
   for (int it = 0; it < 4; it++) xr[it] = __builtin_nontemporal_load((const u32x4*)(x0 + min(it * 8 + rsub, nvalid - 1) * pitch + 8 * c));
 }
-template <int IT0 = 0, int IT1 = 4>      // passes [IT0, IT1) of 8 rows each (the one-pass backward parks 16 rows at a time: `tile` then points 16 * (IT0 / 2) rows in front of the parked ones)
 __device__ __forceinline__ void qk_bwd_tile(const float* tile, float mul, int lane, int nvalid, const bf16_t* x0, bf16_t* o0, int64_t pitch,
                                             const float* w, const float* cs0, const float* sn0, float* sdw, const u32x4* xpre = nullptr) {
   const int c = lane & 7, rsub = lane >> 3;
@@ -188,10 +175,10 @@ __device__ __forceinline__ void qk_bwd_tile(const float* tile, float mul, int la
   u32x4 xr[4];
   if (xpre) {      // (compile-time at every call site: the caller requested the rows earlier -- qk_bwd_rows -- so that their latency lies under its barriers)
 #pragma unroll
-    for (int it = IT0; it < IT1; it++) xr[it] = xpre[it];
+    for (int it = 0; it < 4; it++) xr[it] = xpre[it];
   } else {
 #pragma unroll
-    for (int it = IT0; it < IT1; it++) xr[it] = __builtin_nontemporal_load((const u32x4*)(x0 + min(it * 8 + rsub, nvalid - 1) * pitch + 8 * c));   // (last use of the saved projection)
+    for (int it = 0; it < 4; it++) xr[it] = __builtin_nontemporal_load((const u32x4*)(x0 + min(it * 8 + rsub, nvalid - 1) * pitch + 8 * c));   // (last use of the saved projection)
   }
   // Round 6 (profiles/r06_epilogue_waits.txt).  Loads and stores of a wave retire through ONE in-order counter: a pass that requests its RoPE factors
   // behind the previous pass's store waits for that store, and the compiler's count is exact only in straight-line code.  FULL (all 32 rows exist:
@@ -209,9 +196,9 @@ __device__ __forceinline__ void qk_bwd_tile(const float* tile, float mul, int la
       ld8(tc + rq * 64 + 8 * c, c8);
       ld8(ts + rq * 64 + 8 * c, s8);
     };
-    request(IT0);
+    request(0);
 #pragma unroll
-    for (int it = IT0; it < IT1; it++) {
+    for (int it = 0; it < 4; it++) {
       const int r = it * 8 + rsub;
       const bool valid = FULL || r < nvalid;
       float dz[8], x[8];
@@ -228,7 +215,7 @@ __device__ __forceinline__ void qk_bwd_tile(const float* tile, float mul, int la
           dz[2 * p + 1] = dbv * c8[2 * p + 1] - da * s8[2 * p];
         }
       }
-      if (it + 1 < IT1) request(it + 1);      // (the factors of this pass are dead: same registers; before this pass's store)
+      if (it + 1 < 4) request(it + 1);      // (the factors of this pass are dead: same registers; before this pass's store)
       float ss = 0.f;
 #pragma unroll
       for (int e = 0; e < 8; e++) ss += x[e] * x[e];
@@ -248,7 +235,7 @@ __device__ __forceinline__ void qk_bwd_tile(const float* tile, float mul, int la
       if (valid) st8(o0 + r * pitch + 8 * c, o);
     }
   };
-  if (nvalid >= 8 * IT1) body(std::integral_constant<bool, true>{});
+  if (nvalid >= 32) body(std::integral_constant<bool, true>{});
   else body(std::integral_constant<bool, false>{});
   // the wave's 32 rows: lanes with equal c hold partial sums for features 8c .. 8c+7 (lane bits 5:3 = row lane)
 #pragma unroll
@@ -261,11 +248,10 @@ __device__ __forceinline__ void qk_bwd_tile(const float* tile, float mul, int la
   }
 }
 // dV rows: no arithmetic, the LDS round trip only makes the stores whole 128-byte rows
-template <int IT0 = 0, int IT1 = 4>
 __device__ __forceinline__ void rows_from_tile(const float* tile, int lane, int nvalid, bf16_t* o0, int64_t pitch) {
   const int c = lane & 7, rsub = lane >> 3;
 #pragma unroll
-  for (int it = IT0; it < IT1; it++) {
+  for (int it = 0; it < 4; it++) {
     const int r = it * 8 + rsub;
     float v[8];
     lds_row8(tile, r, c, v);
@@ -441,7 +427,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_kernel(const bf16_t* __restr
 // One s_waitcnt vmcnt + one s_barrier per tile; every wave issues exactly two pieces per tile (8 waves = 8 + 8 KiB).
 // Round 4: nothing is issued past the last tile (the ring used to reload clamped copies: 3 of 7 + 3 tile copies at S = 410), the Q loads
 // go out first and share the first tile's counted wait, the first MFMA of a score block takes a constant-zero C, scale-and-shift and row
-// sums are packed fp32 pairs: 70 -> 67.5 us.  Workgroup geometry, same box (tools/probes/attn_fwd_geo.sh, waves x ring stages):
+// sums are packed fp32 pairs: 70 -> 67.5 us.  Workgroup geometry, same box (profiles/r04_round4_ab.txt; waves x ring stages; the forced geometries left the source after it):
 // 8x4 70.2, 8x3 69.6, 4x4 104, 4x3 101, 4x2 101 us -- four independent 4-wave workgroups per CU de-phase MFMA and VALU work but copy every
 // K/V tile twice as often, and the LDS-DMA stream (64 KiB per tile step and CU) becomes the limit.
 // ------------------------------------------------------------------------------------------------
@@ -971,9 +957,7 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dkv_kernel(const bf16_t* __r
     stamp();                                 // +1: this tile's chunks have landed and are parked in LDS
     __syncthreads();
     stamp();                                 // +2: ... everybody's
-#ifndef MMDIT_DKV_NO_PREFETCH
     if (jq + 1 < nq) request(jq + 1);
-#endif
     if (active) {
 #pragma unroll
     for (int qb = 0; qb < 2; qb++) {
@@ -1025,9 +1009,6 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dkv_kernel(const bf16_t* __r
     }
     }
     if constexpr (TRACE) { const int done = !active ? 0 : (jq * KT + 32 >= S ? 1 : 2); for (int i = done * 3; i < 6; i++) stamp(); }   // (fixed slot count per tile)
-#ifdef MMDIT_DKV_NO_PREFETCH
-    if (jq + 1 < nq) request(jq + 1);
-#endif
   }
   stamp();                                   // loop end
   if constexpr (FUSE) {
@@ -1071,620 +1052,24 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dkv_kernel(const bf16_t* __r
   stamp();                                   // stores done
 }
 
-#ifdef MMDIT_PROBES
-// ------------------------------------------------------------------------------------------------
-// backward in ONE pass per (batch, head) for S <= 416 (round 6; MMDiT-B at 256^2: S = 410): one workgroup owns the whole problem.
-// EXPERIMENT (probes build, MMDIT_ATTN_ONEPASS=1) -- built, correct (tests/test_kernels_gpu.py::test_attention_bwd_with_fused_qk_norm_rope_backward passes on
-// it at S = 94 and 410, closer to autograd than the two kernels), and SLOWER: profiles/r06_attn_onepass_ab.txt.  MMDiT-B batch 64 (768 problems), one box:
-//     two kernels (dQ 110 + dK/dV 153)                           264 us
-//     this kernel                                                1508 us
-//     ... without the 32 ds_add_f32 per wave and 32-query block   237 us      (MMDIT_OP_DBG=1: the reduction of the eight waves' dQ partials is the whole loss)
-//     ... without dS^T park / transposed read / dQ MFMAs too      227 us      (MMDIT_OP_DBG=2)
-// LDS float atomics retire ~1 lane per 2 clocks on gfx950 (7168 wave instructions per workgroup = 423 us: ~140 clocks each), so the in-LDS reduction the
-// design rests on costs 5 x the kernel.  And the ceiling without ANY reduction is 237 us: 5 instead of 7 GEMM units buys 27 us of 264 once the dQ
-// epilogue, delta and the second pass's idle waves (13 key blocks on 8 waves) are paid -- every non-atomic reduction (partials staged through LDS and
-// added by owners: 150 KB of LDS traffic per 32-query step; full-K dQ by four owner waves from exchanged dS: +14 us and 32 KB of K tiles that do not
-// fit beside the accumulator) gives that back.  The two kernels stay the product.
-// Key-stationary like the dK/dV kernel above (a wave owns 32 keys: S / dP with lane = key, P / dS packed straight from the accumulators into the
-// dV^T / dK^T MFMAs), in two passes over the query tiles (13 key blocks on 8 waves) -- and dQ from the SAME dS instead of a second kernel that
-// recomputes S and dP: the wave parks its dS block transposed in a private LDS tile ([key][query], 80-byte rows), reads it back with
-// ds_read_b64_tr_b16 as the A operand of dQ[q][d] += dS[q][key] K[key][d] (B = the wave's K rows, transposed fragments held in registers), and adds
-// the 32 x 64 partial -- lane = feature, so an instruction covers 32 consecutive floats of two rows: conflict-free -- into an fp32 accumulator of the
-// whole dQ in LDS (416 x 68 floats, the layout qk_bwd_tile reads) with ds_add_f32.  No S / dP recomputation (5 instead of 7 GEMM units), Q / K / V /
-// dO / O are read once per pass from L2 instead of twice from HBM, delta = rowsum(dO O) is formed where the dO tile is parked.  The QK-norm / RoPE
-// backward epilogues are those of the two kernels above: dK / dV per pass (parked 16 rows at a time: the LDS left beside the dQ accumulator), dQ at the end
-// straight out of the accumulator.
-// ------------------------------------------------------------------------------------------------
-constexpr int OP_MAXB = 13;                                    // 32-row blocks of S
-constexpr int OP_DST = 80;                                     // byte pitch of a wave's dS^T tile (32 queries x 2 B + 16)
-constexpr int OP_DQ_BYTES = OP_MAXB * QK_WAVE_BYTES;           // 113152: the dQ accumulator
-constexpr int OP_R_DST0 = 2 * KT * 128 + 2 * KT * 4;           // 16896: Q tile, dO tile, lse, delta in front of the dS^T tiles
-constexpr int OP_R_BYTES = OP_R_DST0 + 8 * 32 * OP_DST;        // 37376 (>= 8 x 4 KB of K rows, >= 8 x 16 parked rows)
-constexpr int OP_LDS = OP_DQ_BYTES + OP_R_BYTES + 256 * 4;     // 151552
-
-__global__ __launch_bounds__(512) void attn_bwd_onepass_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
-                                                               const bf16_t* __restrict__ Ox, const bf16_t* __restrict__ Oc,
-                                                               const bf16_t* __restrict__ dOx, const bf16_t* __restrict__ dOc, const float* __restrict__ lse,
-                                                               int BH, int H, int S, int n_img, float scale, QkFuse F, int dbg) {
-  constexpr int NT = 512;
-  extern __shared__ __attribute__((aligned(16))) char smem_dyn[];
-  float* dqa = (float*)smem_dyn;
-  char* R = smem_dyn + OP_DQ_BYTES;
-  char* qtile = R;
-  char* dotile = R + KT * 128;
-  float* lse_s = (float*)(R + 2 * KT * 128);
-  float* del_s = lse_s + KT;
-  float* sdw = (float*)(smem_dyn + OP_DQ_BYTES + OP_R_BYTES);      // [q: image | text][64], [k: image | text][64]
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  char* dst_w = R + OP_R_DST0 + wave * (32 * OP_DST);
-  int tile0, bh;
-  map_block(1, BH, tile0, bh);
-  const int h = bh % H;
-  const int64_t b = bh / H;
-  const bf16_t* Qb = Q + (int64_t)bh * S * HD;
-  const bf16_t* Kb = K + (int64_t)bh * S * HD;
-  const bf16_t* Vb = V + (int64_t)bh * S * HD;
-  const int n_txt = S - n_img, D = H * HD;
-  const int64_t pitch = 3 * (int64_t)D;
-  const int nkb = (S + 31) >> 5, nq = (S + KT - 1) / KT;
-
-  for (int i = tid; i < OP_DQ_BYTES / 16; i += NT) *LDS_PTR(f32x4, dqa + 4 * i) = (f32x4){0.f, 0.f, 0.f, 0.f};
-  if (tid < 256) sdw[tid] = 0.f;
-
-  u32x4 sq[1], sd[1], so[1];
-  float lv = 0.f;
-  auto request = [&](int jq) {
-    tile_g2r<NT>(sq, Qb, jq * KT, S, tid);
-    const int row = tid >> 3, kc = tid & 7, sidx = jq * KT + row;
-    const bf16_t* pd = sidx < S ? tok_ptr(dOx, dOc, b, sidx, n_img, n_txt, D, h) : nullptr;
-    const bf16_t* po = sidx < S ? tok_ptr(Ox, Oc, b, sidx, n_img, n_txt, D, h) : nullptr;
-    sd[0] = pd ? *(const u32x4*)(pd + kc * 8) : (u32x4){0, 0, 0, 0};
-    so[0] = (pd && po) ? *(const u32x4*)(po + kc * 8) : (u32x4){0, 0, 0, 0};
-    lv = 0.f;
-    if (tid < KT && jq * KT + tid < S) lv = lse[(int64_t)bh * S + jq * KT + tid];
-  };
-
-#pragma unroll 1
-  for (int pass = 0; pass * 8 < nkb; pass++) {
-    const int kblk = pass * 8 + wave;
-    const bool active = kblk < nkb;                                  // (wave-uniform)
-    const int key = kblk * 32 + (lane & 31), keyc = min(key, S - 1);
-    const bool ragged_keys = kblk * 32 + 32 > S;                     // (wave-uniform) this wave's block holds padding keys
-    __syncthreads();                                                 // R is free: the zero fill / the previous pass's epilogue is done
-    bf16x8 kf[4], vf[4], kt[2][2];
-#pragma unroll
-    for (int ks = 0; ks < 4; ks++) {
-      kf[ks] = *(const bf16x8*)(Kb + (int64_t)keyc * HD + ks * 16 + (lane >> 5) * 8);
-      vf[ks] = *(const bf16x8*)(Vb + (int64_t)keyc * HD + ks * 16 + (lane >> 5) * 8);
-    }
-    {   // the wave's 32 K rows as a (swizzled) tile: its transposed fragments are the B operand of the dQ MFMAs
-      char* kw = R + wave * 4096;
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const int c = lane + 64 * i, row = c >> 3, kc = c & 7;
-        const u32x4 v = *(const u32x4*)(Kb + (int64_t)min(kblk * 32 + row, S - 1) * HD + kc * 8);
-        *LDS_PTR(u32x4, kw + row * 128 + ((kc ^ sw2(row)) << 4)) = v;
-      }
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int h8 = 0; h8 < 2; h8++)
-#pragma unroll
-        for (int db = 0; db < 2; db++) kt[h8][db] = tr_frag_d(kw, 0, h8, db, lane);
-    }
-    f32x16 dk[2], dv[2];
-#pragma unroll
-    for (int db = 0; db < 2; db++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) { dk[db][r] = 0.f; dv[db][r] = 0.f; }
-    request(0);
-#pragma unroll 1
-    for (int jq = 0; jq < nq; jq++) {
-      __syncthreads();                                               // everyone has left the previous tile (jq = 0: has taken its K fragments out of R)
-      tile_r2s_sw<NT>(sq, qtile, tid);
-      tile_r2s_sw<NT>(sd, dotile, tid);
-      {   // delta = rowsum(dO * O): 8 lanes hold a row
-        float dl = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; e++)
-          dl += __builtin_bit_cast(float, so[0][e] << 16) * __builtin_bit_cast(float, sd[0][e] << 16) +
-                __builtin_bit_cast(float, so[0][e] & 0xffff0000u) * __builtin_bit_cast(float, sd[0][e] & 0xffff0000u);
-        dl = sum8(dl);
-        if ((tid & 7) == 0) del_s[tid >> 3] = dl;
-      }
-      if (tid < KT) lse_s[tid] = lv * LOG2E;
-      __syncthreads();
-      if (jq + 1 < nq) request(jq + 1);
-      if (active) {
-#pragma unroll 1
-        for (int qb = 0; qb < 2; qb++) {
-          if (jq * KT + qb * 32 >= S) continue;                      // (wave-uniform) 32 padding queries contribute nothing
-          f32x16 sacc, dp;
-#pragma unroll
-          for (int r = 0; r < 16; r++) { sacc[r] = 0.f; dp[r] = 0.f; }
-#pragma unroll
-          for (int ks = 0; ks < 4; ks++) {
-            sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag_d(qtile, qb * 32, ks, lane), kf[ks], sacc, 0, 0, 0);
-            dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag_d(dotile, qb * 32, ks, lane), vf[ks], dp, 0, 0, 0);
-          }
-          f32x16 ds;
-#pragma unroll
-          for (int g = 0; g < 4; g++) {
-            const int r0 = qb * 32 + 8 * g + 4 * (lane >> 5);
-            const f32x4 l4 = *LDS_PTR(const f32x4, lse_s + r0);
-            const f32x4 d4 = *LDS_PTR(const f32x4, del_s + r0);
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-              const int r = g * 4 + e;
-              const float pe = fast_exp2(fmaf(sacc[r], scale * LOG2E, -l4[e]));
-              sacc[r] = pe;
-              ds[r] = pe * (dp[r] - d4[e]);
-            }
-          }
-          if ((jq + 1) * KT > S) {                                   // padding queries: the last tile only
-#pragma unroll
-            for (int g = 0; g < 4; g++)
-#pragma unroll
-              for (int e = 0; e < 4; e++)
-                if (jq * KT + qb * 32 + 8 * g + 4 * (lane >> 5) + e >= S) { sacc[g * 4 + e] = 0.f; ds[g * 4 + e] = 0.f; }
-          }
-          if (ragged_keys && key >= S) {                             // padding keys must not reach dQ (their dK / dV columns are simply not stored)
-#pragma unroll
-            for (int r = 0; r < 16; r++) ds[r] = 0.f;
-          }
-          // dS^T into the wave's tile: row = key, 4 consecutive queries per 8-byte write
-#pragma unroll
-          for (int g = 0; g < 4; g++) {
-            const u32x2 w2 = {pack_bf2(ds[g * 4], ds[g * 4 + 1]), pack_bf2(ds[g * 4 + 2], ds[g * 4 + 3])};
-            *LDS_PTR(u32x2, dst_w + (lane & 31) * OP_DST + (8 * g + 4 * (lane >> 5)) * 2) = w2;
-          }
-#pragma unroll
-          for (int h8 = 0; h8 < 2; h8++) {
-            const bf16x8 pf = pack_frag(sacc, h8), dsf = pack_frag(ds, h8);
-#pragma unroll
-            for (int db = 0; db < 2; db++) {
-              dv[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag_d(dotile, qb * 32, h8, db, lane), pf, dv[db], 0, 0, 0);
-              dk[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag_d(qtile, qb * 32, h8, db, lane), dsf, dk[db], 0, 0, 0);
-            }
-          }
-          __builtin_amdgcn_wave_barrier();
-          if (dbg & 2) continue;
-          const bf16x8 a0 = tr_frag(dst_w, OP_DST, 0, 0, 0, lane), a1 = tr_frag(dst_w, OP_DST, 0, 1, 0, lane);      // lane = query, k-slots = this wave's keys
-          // dq: lane = feature 32 db + (lane & 31), register r = query acc_row(r, lane) of the block
-          float* dst = dqa + (jq * KT + qb * 32 + 4 * (lane >> 5)) * QK_ROW_F + (lane & 31);
-#pragma unroll
-          for (int db = 0; db < 2; db++) {
-            f32x16 dq;
-#pragma unroll
-            for (int r = 0; r < 16; r++) dq[r] = 0.f;
-            dq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, kt[0][db], dq, 0, 0, 0);
-            dq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, kt[1][db], dq, 0, 0, 0);
-            if (dbg & 1) { asm volatile("" ::"v"(dq[0]), "v"(dq[5]), "v"(dq[15])); continue; }
-#pragma unroll
-            for (int r = 0; r < 16; r++)
-              __hip_atomic_fetch_add(LDS_PTR(float, dst + ((r & 3) + 8 * (r >> 2)) * QK_ROW_F + 32 * db), dq[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          }
-          __builtin_amdgcn_wave_barrier();                           // (the dS^T tile is rewritten by the next block)
-        }
-      }
-    }
-    // ---- dK / dV of this pass: QK-norm / RoPE backward from 16 parked rows at a time ------------------------------------------------------
-    __syncthreads();                                                 // every wave has left the last Q / dO tile: R is free
-    if (active) {
-      float* t16 = (float*)(R + wave * (16 * QK_ROW_F * 4));
-      const int k0 = kblk * 32;
-      const bool img = k0 < n_img;                                   // wave-uniform: n_img % 32 == 0
-      const int tok0 = img ? k0 : k0 - n_img, nvalid = min(32, (img ? n_img : S) - k0);
-      const int64_t off = (img ? b * n_img + tok0 : b * n_txt + tok0) * pitch + D + h * HD;
-      const bf16_t* xb = (img ? F.qkv_x : F.qkv_c) + off;
-      bf16_t* ob = (img ? F.dqkv_x : F.dqkv_c) + off;
-      const float* wk = img ? F.wk_x : F.wk_c;
-      const float* cs = img ? F.rcos + (int64_t)tok0 * 64 : nullptr;
-      const float* sn = img ? F.rsin + (int64_t)tok0 * 64 : nullptr;
-      float* sk = sdw + 128 + (img ? 0 : 64);
-      acc_to_lds_half(dk, t16, lane, 0);
-      qk_bwd_tile<0, 2>(t16, scale, lane, nvalid, xb, ob, pitch, wk, cs, sn, sk);
-      __builtin_amdgcn_wave_barrier();
-      acc_to_lds_half(dk, t16, lane, 1);
-      qk_bwd_tile<2, 4>(t16 - 16 * QK_ROW_F, scale, lane, nvalid, xb, ob, pitch, wk, cs, sn, sk);
-      __builtin_amdgcn_wave_barrier();
-      acc_to_lds_half(dv, t16, lane, 0);
-      rows_from_tile<0, 2>(t16, lane, nvalid, ob + D, pitch);
-      __builtin_amdgcn_wave_barrier();
-      acc_to_lds_half(dv, t16, lane, 1);
-      rows_from_tile<2, 4>(t16 - 16 * QK_ROW_F, lane, nvalid, ob + D, pitch);
-    }
-  }
-  // ---- dQ: straight out of the accumulator -----------------------------------------------------------------------------------------------
-  __syncthreads();
-#pragma unroll 1
-  for (int blk = wave; blk < nkb; blk += 8) {
-    const int q0 = blk * 32;
-    const bool img = q0 < n_img;
-    const int tok0 = img ? q0 : q0 - n_img, nvalid = min(32, (img ? n_img : S) - q0);
-    const int64_t off = (img ? b * n_img + tok0 : b * n_txt + tok0) * pitch + h * HD;
-    qk_bwd_tile(dqa + q0 * QK_ROW_F, scale, lane, nvalid, (img ? F.qkv_x : F.qkv_c) + off, (img ? F.dqkv_x : F.dqkv_c) + off, pitch, img ? F.wq_x : F.wq_c,
-                img ? F.rcos + (int64_t)tok0 * 64 : nullptr, img ? F.rsin + (int64_t)tok0 * 64 : nullptr, sdw + (img ? 0 : 64));
-  }
-  __syncthreads();
-  if (tid < 256 && sdw[tid] != 0.f) atomicAdd(F.dw + ((tid >> 6) & 1) * 128 + (tid >> 7) * 64 + (tid & 63), sdw[tid]);      // [wq_x | wk_x | wq_c | wk_c]
-}
-
-#endif
-
-#ifdef MMDIT_PROBES
-// ------------------------------------------------------------------------------------------------
-// backward dK/dV, DE-PHASED (round 4 experiment, probes build only: MMDIT_ATTN_DKV_DP=1).  Same arithmetic and fragment conventions as
-// attn_bwd_dkv_kernel above, another schedule.  MEASURED SLOWER than that kernel (backward of one block, S = 410, 64 x 12 heads, same box:
-// 264.9 vs 248.5 us; correct: the attention tests pass with it), so it is not the product path.  Ablations of this kernel (same box, backward =
-// dQ kernel ~105 us + this): full 268; without the stagger 272; no exponentials 262; no MFMAs 243; no LDS fragment reads 263; no DMA in the loop
-// 260; no MFMAs + no LDS reads + no exponentials 188 -- the pieces are small and nearly additive, and ~80 us remain without them: the fused
-// QK-norm / RoPE epilogue (HBM-bound row traffic, one workgroup per CU: nothing to overlap with), the launch and first-tile latency of six
-// rounds of workgroups, barriers and the non-transcendental VALU work.  De-phasing attacks MFMA / VALU serialisation, which is not where this
-// kernel's time is.  There a tile's phases -- S / dP MFMAs, softmax-backward VALU work, dV / dK MFMAs, each behind LDS fragment reads -- run
-// one after the other, because two workgroup barriers per tile put all eight waves into the same phase (cycle stamps, round 3: 5700 cycles
-// per tile against 2048 of matrix-pipe time).  Here:
-//  * the unit is a BLOCK of 32 queries (two per 64-query tile) with a V phase (the arithmetic of block b: P, dS packed to bf16 fragments) and
-//    an M phase (the dV / dK MFMAs of block b, then the S / dP MFMAs of block b + 1): 16 MFMAs against 16 exponentials + ~50 packed VALU slots;
-//  * the waves form two groups (wave >> 2: the two waves of every SIMD are in different groups) and group 1 runs ONE barrier behind group 0:
-//    between any two consecutive barriers one group is in a V phase and the other in an M phase, so on every SIMD the matrix pipe of one wave
-//    runs beside the VALU work of the other (the 8-phase GEMM's trick, csrc/gemm8p.hip);
-//  * Q / dO tiles (+ their lse / delta rows) go global -> LDS by LDS-DMA into a 4-stage ring (swizzle sw2 on the source address: the layout
-//    tile_r2s_sw writes), two tiles ahead, with counted vmcnt waits; no staging registers, no ds_write.
-// Hazards (barrier intervals: group 0 has V(b) in interval 2b and M(b) in 2b + 1, group 1 one later).  Tile j is read from M(2j - 1) (S / dP of
-// its first block) to M(2j + 1) (dV / dK of its second), i.e. until interval 4j + 4: its stage is refilled (tile j + 4) in M(2j + 2), interval
-// 4j + 5 / 4j + 6.  All LDS fragment reads sit in the M phases (row fragments of block b + 1 first, transposed fragments of block b + 1 behind
-// the dV / dK MFMAs of block b); tile j is first read at the start of M(2j - 1), and the wait for it sits at the end of V(2j - 2) of every
-// wave (interval <= 4j - 3), two barriers earlier.
-// ------------------------------------------------------------------------------------------------
-constexpr int DKV_ST = 4;                            // ring stages (a power of two)
-constexpr int DKV_STB = 2 * KT * 128 + 2 * KT * 4;   // 16896 B: Q tile, dO tile, lse row, delta row
-template <bool FUSE> constexpr int dkv_lds_bytes() { return FUSE && qk_lds_bytes<8>() > DKV_ST * DKV_STB ? qk_lds_bytes<8>() : DKV_ST * DKV_STB; }
-
-__device__ __forceinline__ void attn_glds4(const void* gptr, uint32_t lds_dst_) {    // 4 bytes per lane: 256 B per instruction
-  const uint32_t lds_dst = __builtin_amdgcn_readfirstlane(lds_dst_);
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" ::"v"(gptr), "s"(lds_dst) : "memory", "m0");
-}
-
-template <typename TG, bool FUSE, bool TRACE = false>
-__global__ __launch_bounds__(512) void attn_bwd_dkv_dp_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
-                                                              const bf16_t* __restrict__ dOx, const bf16_t* __restrict__ dOc,
-                                                              const float* __restrict__ lse, const float* __restrict__ delta,
-                                                              int BH, int H, int S, int n_img, float scale, TG* __restrict__ dK, TG* __restrict__ dV, QkFuse F = QkFuse(),
-                                                              unsigned long long* __restrict__ trace = nullptr) {
-  constexpr int NW = 8;
-  // TRACE (tools/probes/attn_bwd_trace.py --dp): lane 0 of every wave stamps the cycle counter: 0 start, 1 prologue done (first S / dP issued);
-  // per block: +0 V-phase arithmetic issued, +1 past the barrier, +2 row reads + DMA issued, +3 dV / dK MFMAs issued, +4 S / dP MFMAs issued and past
-  // the second barrier
-  int tpos = 0;
-  auto stamp = [&]() {
-    if constexpr (TRACE) {
-      if (blockIdx.x < 2048 && (threadIdx.x & 63) == 0 && tpos < 72) trace[((int64_t)blockIdx.x * NW + (threadIdx.x >> 6)) * 72 + tpos] = __builtin_readcyclecounter();
-      tpos++;
-    }
-  };
-  stamp();
-  extern __shared__ __attribute__((aligned(16))) char smem[];      // dkv_lds_bytes<FUSE>(): the ring; afterwards the fused epilogue's tiles
-#ifdef MMDIT_DKV_GRP_LSB     // experiment: which waves share a SIMD?
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), grp = wave & 1;
-#else
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), grp = wave >> 2;
-#endif
-  MMDIT_YOUNG_HALF_PRIO();
-  const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(char, smem);
-  int ktile, bh;
-  map_block((S + 32 * NW - 1) / (32 * NW), BH, ktile, bh);
-  const int h = bh % H;
-  const int64_t b = bh / H;
-  const bf16_t* Qb = Q + (int64_t)bh * S * HD;
-  const bf16_t* Kb = K + (int64_t)bh * S * HD;
-  const bf16_t* Vb = V + (int64_t)bh * S * HD;
-  const int key = ktile * 32 * NW + wave * 32 + (lane & 31);
-  const bool active = ktile * 32 * NW + wave * 32 < S;   // wave-uniform: a wave whose 32 keys are all padding only helps with the tile copies
-  const int keyc = min(key, S - 1);
-  const int n_txt = S - n_img, D = H * HD;
-  const int nq = (S + KT - 1) / KT, nblk = (S + 31) / 32;
-
-  // K / V fragments of this lane's key: requested first (asm: the compiler must not put a vmcnt(0) of its own in front of their first use --
-  // it cannot see the DMA queue); the first tile's counted wait covers them, the empty asm behind it carries the dependence
-  bf16x8 kf[4], vf[4];
-#pragma unroll
-  for (int ks = 0; ks < 4; ks++) {
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(kf[ks]) : "v"(Kb + (int64_t)keyc * HD + ks * 16 + (lane >> 5) * 8) : "memory");
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(vf[ks]) : "v"(Vb + (int64_t)keyc * HD + ks * 16 + (lane >> 5) * 8) : "memory");
-  }
-  // this lane's 16 bytes of a Q / dO tile: row 8 * wave + (lane >> 3), LDS slot lane & 7 holds chunk slot ^ sw2(row); rows past the end re-read
-  // the last query (masked in the ragged block).  Wave 0 also copies the tile's 64 lse and delta values (4 bytes per lane).
-  const int rl = 8 * wave + (lane >> 3), dcol = ((lane & 7) ^ sw2(rl)) * 8;
-  auto issue = [&](int t) {
-    const uint32_t base = lds0 + (t & (DKV_ST - 1)) * DKV_STB;
-    const int row = min(t * KT + rl, S - 1);
-    attn_glds16(Qb + (int64_t)row * HD + dcol, base + wave * 1024);
-    attn_glds16(tok_ptr(dOx, dOc, b, row, n_img, n_txt, D, h) + dcol, base + KT * 128 + wave * 1024);
-    if (wave == 0) {
-      const int64_t r1 = (int64_t)bh * S + min(t * KT + lane, S - 1);
-      attn_glds4(lse + r1, base + 2 * KT * 128);
-      attn_glds4(delta + r1, base + 2 * KT * 128 + KT * 4);
-    }
-  };
-  auto wait_tiles = [&](int n) {      // all but the n youngest tiles of this wave's requests have landed (n = 0, 1, 2)
-    if (wave == 0) {
-      if (n >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else if (n == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-      if (n >= 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else if (n == 1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-  };
-#pragma unroll
-  for (int t = 0; t < DKV_ST - 1; t++)
-    if (t < nq) issue(t);
-
-  f32x16 dk[2], dv[2];
-#pragma unroll
-  for (int db = 0; db < 2; db++)
-#pragma unroll
-    for (int r = 0; r < 16; r++) { dk[db][r] = 0.f; dv[db][r] = 0.f; }
-  // per-lane LDS offsets of the fragment reads (tile / block / k-step parts are immediates: sw2 only involves row bits 1..3)
-  uint32_t rowoff[4], troff[2][2];
-  {
-    const int l31 = lane & 31, hi = lane >> 5;
-#pragma unroll
-    for (int ks = 0; ks < 4; ks++) rowoff[ks] = l31 * 128 + (((ks * 2 + hi) ^ sw2(l31)) << 4);
-    const int row0 = 4 * hi + ((lane & 15) >> 2);
-#pragma unroll
-    for (int cb = 0; cb < 2; cb++) {
-      const int cbyte = (cb * 32 + 16 * ((lane >> 4) & 1) + (lane & 3) * 4) * 2;
-      troff[cb][0] = row0 * 128 + ((((cbyte >> 4) ^ sw2(row0)) << 4) | (cbyte & 15));
-      troff[cb][1] = (row0 + 8) * 128 + ((((cbyte >> 4) ^ sw2(row0 + 8)) << 4) | (cbyte & 15));
-    }
-  }
-  const float c = scale * LOG2E;
-  f32x16 s, dp;
-  bf16x8 pf[2], dsf[2];
-  constexpr f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  auto tile_of = [&](int bq) { return smem + ((bq >> 1) & (DKV_ST - 1)) * DKV_STB; };
-  // fragment registers of an M phase: ALL LDS reads of the phase are requested before its first MFMA (the compiler's own order -- read two,
-  // wait, multiply -- left ~600 cycles of LDS latency per phase exposed, during which the SIMD's matrix pipe idled: the other wave is in
-  // its V phase)
-  bf16x8 fq[4], fo[4];       // row fragments of Q / dO (block bq + 1)
-  s16x4 tq4[2][2][2], to4[2][2][2];   // transposed fragments of Q / dO (block bq): [h8][db][low | high half]
-  auto read_rows = [&](int bq) {
-#ifdef MMDIT_DKV_NOLDS           // ablation: no LDS fragment reads (wrong results)
-#pragma unroll
-    for (int ks = 0; ks < 4; ks++) { fq[ks] = kf[ks]; fo[ks] = vf[ks]; }
-    return;
-#endif
-    const char* tq = tile_of(bq) + (bq & 1) * 32 * 128;
-#pragma unroll
-    for (int ks = 0; ks < 4; ks++) {
-      fq[ks] = *LDS_PTR(const bf16x8, tq + rowoff[ks]);
-      fo[ks] = *LDS_PTR(const bf16x8, tq + KT * 128 + rowoff[ks]);
-    }
-  };
-  auto read_tr = [&](int bq) {
-#ifdef MMDIT_DKV_NOLDS
-#pragma unroll
-    for (int h8 = 0; h8 < 2; h8++)
-#pragma unroll
-      for (int db = 0; db < 2; db++)
-#pragma unroll
-        for (int w = 0; w < 2; w++) { to4[h8][db][w] = (s16x4){1, 2, 3, (short)bq}; tq4[h8][db][w] = (s16x4){4, 3, 2, (short)bq}; }
-    return;
-#endif
-    const char* tq = tile_of(bq) + (bq & 1) * 32 * 128;
-#pragma unroll
-    for (int h8 = 0; h8 < 2; h8++)
-#pragma unroll
-      for (int db = 0; db < 2; db++)
-#pragma unroll
-        for (int w = 0; w < 2; w++) {
-          to4[h8][db][w] = lds_tr16(tq + h8 * 16 * 128 + KT * 128 + troff[db][w]);
-          tq4[h8][db][w] = lds_tr16(tq + h8 * 16 * 128 + troff[db][w]);
-        }
-  };
-  auto mfma_sdp = [&]() {        // S = Q K^T, dP = dO V^T of the block whose row fragments were read (rows = queries, lane = key)
-#ifdef MMDIT_DKV_NOMFMA          // ablation: no MFMAs (wrong results)
-#pragma unroll
-    for (int ks = 0; ks < 4; ks++) { s[ks] = (float)fq[ks][0]; dp[ks] = (float)fo[ks][0]; }
-    return;
-#endif
-#pragma unroll
-    for (int ks = 0; ks < 4; ks++) {
-      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fq[ks], kf[ks], ks == 0 ? zero16 : s, 0, 0, 0);
-      dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fo[ks], vf[ks], ks == 0 ? zero16 : dp, 0, 0, 0);
-    }
-  };
-  auto softmax_bwd = [&](int bq) {     // P = exp2(S c - lse), dS = P (dP - delta): packed fp32 pairs; -> bf16 fragments
-    const char* tl = tile_of(bq) + 2 * KT * 128;
-    const int qb = bq & 1, hi = lane >> 5;
-    f32x16 ds;
-    f32x4 lq[4], dq4[4];       // all eight (broadcast) reads first: one exposed LDS latency per phase instead of one per group
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-      const int r0 = qb * 32 + 8 * g + 4 * hi;
-      lq[g] = *LDS_PTR(const f32x4, tl + r0 * 4);
-      dq4[g] = *LDS_PTR(const f32x4, tl + KT * 4 + r0 * 4);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int g = 0; g < 4; g++) {
-      const f32x4 l4 = lq[g], d4 = dq4[g];
-#pragma unroll
-      for (int e = 0; e < 4; e += 2) {
-        const int r = g * 4 + e;
-        const f32x2 sv = {s[r], s[r + 1]}, dpv = {dp[r], dp[r + 1]};
-        const f32x2 nl = (f32x2){l4[e], l4[e + 1]} * (f32x2){-LOG2E, -LOG2E};
-        const f32x2 t = __builtin_elementwise_fma(sv, (f32x2){c, c}, nl);
-#ifdef MMDIT_DKV_NOEXP          // ablation: no exponentials (wrong results)
-        const f32x2 pv = t;
-#else
-        const f32x2 pv = {fast_exp2(t[0]), fast_exp2(t[1])};
-#endif
-        const f32x2 dsv = pv * (dpv - (f32x2){d4[e], d4[e + 1]});
-        s[r] = pv[0]; s[r + 1] = pv[1];
-        ds[r] = dsv[0]; ds[r + 1] = dsv[1];
-      }
-    }
-    // Padding QUERIES exist in the last block only (their tile rows are copies of the last query): P and dS are zeroed there in a
-    // wave-uniform branch.  A lane whose key is padding works on the clamped last key and its dK / dV column is never stored.
-    if ((bq + 1) * 32 > S) {
-#pragma unroll
-      for (int g = 0; g < 4; g++)
-#pragma unroll
-        for (int e = 0; e < 4; e++)
-          if (bq * 32 + 8 * g + 4 * hi + e >= S) { s[g * 4 + e] = 0.f; ds[g * 4 + e] = 0.f; }
-    }
-#pragma unroll
-    for (int h8 = 0; h8 < 2; h8++) { pf[h8] = pack_frag(s, h8); dsf[h8] = pack_frag(ds, h8); }
-  };
-  auto mfma_dkv = [&]() {        // dV^T += dO^T P, dK^T += Q^T dS of the block whose transposed fragments were read
-#ifdef MMDIT_DKV_NOMFMA
-#pragma unroll
-    for (int h8 = 0; h8 < 2; h8++)
-#pragma unroll
-      for (int db = 0; db < 2; db++) { dv[db][h8] += (float)to4[h8][db][0][0] + (float)to4[h8][db][1][0] + (float)pf[h8][0]; dk[db][h8] += (float)tq4[h8][db][0][0] + (float)tq4[h8][db][1][0] + (float)dsf[h8][0]; }
-    return;
-#endif
-#pragma unroll
-    for (int h8 = 0; h8 < 2; h8++)
-#pragma unroll
-      for (int db = 0; db < 2; db++) {
-        const s16x4 olo = to4[h8][db][0], ohi = to4[h8][db][1], qlo = tq4[h8][db][0], qhi = tq4[h8][db][1];
-        const s16x8 of = {olo[0], olo[1], olo[2], olo[3], ohi[0], ohi[1], ohi[2], ohi[3]};
-        const s16x8 qf = {qlo[0], qlo[1], qlo[2], qlo[3], qhi[0], qhi[1], qhi[2], qhi[3]};
-        dv[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, of), pf[h8], dv[db], 0, 0, 0);
-        dk[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, qf), dsf[h8], dk[db], 0, 0, 0);
-      }
-  };
-  auto bar = [&]() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); };
-
-  wait_tiles(min(2, nq - 1));
-  asm volatile("" : "+v"(kf[0]), "+v"(kf[1]), "+v"(kf[2]), "+v"(kf[3]), "+v"(vf[0]), "+v"(vf[1]), "+v"(vf[2]), "+v"(vf[3]));
-  bar();                                   // tile 0 has landed for every wave
-  if (active) { read_rows(0); mfma_sdp(); read_tr(0); }
-  stamp();
-#ifndef MMDIT_DKV_NOSTAGGER    // (experiment: both groups in the same phase -- the same code as a lockstep kernel)
-  if (grp == 1) bar();                     // group 1 runs one barrier behind from here on
-#endif
-  for (int bq = 0; bq < nblk; bq++) {
-    // ---- V phase: the arithmetic of block bq (pure VALU work); at its end the wait for tile (bq >> 1) + 1, first read in the NEXT M phase
-    if (active) softmax_bwd(bq);
-    stamp();
-#ifdef MMDIT_DKV_NODMA
-    if (bq == 0) wait_tiles(0);
-#else
-    if (!(bq & 1)) wait_tiles(max(0, min(1, nq - 2 - (bq >> 1))));
-#endif
-    __builtin_amdgcn_s_barrier();
-    stamp();
-    // ---- M phase.  ALL LDS fragment traffic lives here, between the MFMAs (the V phase is pure VALU work): the row fragments of block
-    // bq + 1 are requested first and arrive under the dV / dK MFMAs of block bq (whose transposed fragments were requested in the previous
-    // M phase); the transposed fragments of block bq + 1 are requested behind those MFMAs and arrive under the S / dP MFMAs and the V phase.
-    if (active && bq + 1 < nblk) read_rows(bq + 1);
-    const int t2 = (bq >> 1) + DKV_ST - 1;
-#ifndef MMDIT_DKV_NODMA          // (ablation: the loop re-reads the first three tiles)
-    if (!(bq & 1) && t2 < nq) issue(t2);   // refill the stage of tile (bq >> 1) - 1: every wave left it two barriers ago
-#endif
-    stamp();
-    if (active) {
-      __builtin_amdgcn_sched_barrier(0);
-      mfma_dkv();
-      __builtin_amdgcn_sched_barrier(0);
-      stamp();
-      if (bq + 1 < nblk) { read_tr(bq + 1); __builtin_amdgcn_sched_barrier(0); mfma_sdp(); }
-    } else stamp();
-    __builtin_amdgcn_s_barrier();
-    stamp();
-  }
-#ifndef MMDIT_DKV_NOSTAGGER
-  if (grp == 0) bar();                     // rejoin
-#endif
-  __syncthreads();                         // every wave has left the ring
-  if constexpr (FUSE) {
-    // dK rows -> gradient of the raw k projection (qk_bwd_tile), dV rows into the v part of the same output rows
-    float* sdw = (float*)(smem + NW * QK_WAVE_BYTES);             // [image | text][64]
-    if (tid < 128) sdw[tid] = 0.f;
-    __syncthreads();
-    if (active) {
-      const int k0 = ktile * 32 * NW + wave * 32;
-      const bool img = k0 < n_img;                                   // wave-uniform: n_img % 32 == 0
-      const int tok0 = img ? k0 : k0 - n_img, nvalid = min(32, (img ? n_img : S) - k0);
-      const int64_t pitch = 3 * (int64_t)D, off = (img ? b * n_img + tok0 : b * n_txt + tok0) * pitch + D + h * HD;
-      bf16_t* ob = (img ? F.dqkv_x : F.dqkv_c) + off;
-      float* tile = (float*)(smem + wave * QK_WAVE_BYTES);
-      acc_to_lds(dk, tile, lane);
-      qk_bwd_tile(tile, scale, lane, nvalid, (img ? F.qkv_x : F.qkv_c) + off, ob, pitch, img ? F.wk_x : F.wk_c,
-                  img ? F.rcos + (int64_t)tok0 * 64 : nullptr, img ? F.rsin + (int64_t)tok0 * 64 : nullptr, sdw + (img ? 0 : 64));
-      __builtin_amdgcn_wave_barrier();
-      acc_to_lds(dv, tile, lane);
-      rows_from_tile(tile, lane, nvalid, ob + D, pitch);
-    }
-    __syncthreads();
-    if (tid < 128 && sdw[tid] != 0.f) atomicAdd(F.dw + (tid >> 6) * 128 + 64 + (tid & 63), sdw[tid]);   // [. | wk_x | . | wk_c]
-  } else if (key < S) {
-    TG* pk = dK + ((int64_t)bh * S + key) * HD;
-    TG* pv = dV + ((int64_t)bh * S + key) * HD;
-#pragma unroll
-    for (int db = 0; db < 2; db++)
-#pragma unroll
-      for (int g = 0; g < 4; g++) {
-        float k4[4] = {dk[db][g * 4] * scale, dk[db][g * 4 + 1] * scale, dk[db][g * 4 + 2] * scale, dk[db][g * 4 + 3] * scale};
-        float v4[4] = {dv[db][g * 4], dv[db][g * 4 + 1], dv[db][g * 4 + 2], dv[db][g * 4 + 3]};
-        st4(pk + db * 32 + 8 * g + 4 * (lane >> 5), k4);
-        st4(pv + db * 32 + 8 * g + 4 * (lane >> 5), v4);
-      }
-  }
-}
-#endif   // MMDIT_PROBES
-
-// waves (32 queries / keys each) per workgroup: all waves of a workgroup share one stream of 64-row K/V (or Q/dO) tiles, so
-// 8 waves cut the tile copies and barriers per (batch, head) from 7x to 2x (measured at S = 410: forward 115 -> 70 us,
-// backward 372 -> 271 us).  7-wave workgroups would pad S = 410 less (448 instead of 512 rows) but measured slower (forward 96 vs
-// 70 us: 448 threads copy a 512-chunk tile in two unbalanced passes).  MMDIT_ATTN_NW = 2 | 4 | 6 | 7 | 8 overrides for A/B runs.
-int attn_waves(int S) {
-  (void)S;
-#ifdef MMDIT_PROBES
-  static const char* e = getenv("MMDIT_ATTN_NW");
-  if (e) return atoi(e);
-#endif
-  return 8;
-}
-
 }  // namespace
 
+// Workgroup width of the fast-mode launches below: 8 waves (32 queries / keys each).  All waves of a workgroup share one stream of 64-row K/V (or
+// Q/dO) tiles, so 8 waves instead of 2 cut the tile copies and barriers per (batch, head) from 7x to 2x (measured at S = 410: forward 115 -> 70 us,
+// backward 372 -> 271 us).  7-wave workgroups would pad S = 410 less (448 instead of 512 rows) but measured slower (forward 96 vs 70 us: 448
+// threads copy a 512-chunk tile in two unbalanced passes).
 extern "C" int mmdit_attn_fwd(const void* Q, const void* K, const void* V, int batch, int heads, int S, int n_img, float scale, int mode,
                               void* Ox, void* Oc, float* lse, mmdit_stream_t stream) {
   MMDIT_CHECK_ARG(Q && K && V && Ox && lse && batch > 0 && heads > 0 && S > 0 && n_img > 0 && n_img <= S);
   MMDIT_CHECK_ARG(Oc || n_img == S);
   hipStream_t s = (hipStream_t)stream;
-  const int nw = attn_waves(S);
-#define MMDIT_FWD(NW, OR) hipLaunchKernelGGL((attn_fwd_kernel<NW, OR>), dim3(((S + 32 * NW - 1) / (32 * NW)) * batch * heads), dim3(NW * 64), 0, s, (const bf16_t*)Q, (const bf16_t*)K, \
-                                             (const bf16_t*)V, batch * heads, heads, S, n_img, scale, (bf16_t*)Ox, (bf16_t*)Oc, lse)
-  if (mode == 1) MMDIT_FWD(2, true);                 // the reference's rounding points (parity mode)
-  else if (mode != 0) return MMDIT_ERR_ARG;
-#ifdef MMDIT_PROBES                                   // experiments: the register-staged kernel at a forced workgroup width (MMDIT_ATTN_DMA=0 / MMDIT_ATTN_NW)
-  else if ((getenv("MMDIT_ATTN_DMA") && atoi(getenv("MMDIT_ATTN_DMA")) == 0) || getenv("MMDIT_ATTN_NW")) {
-    if (nw == 8) MMDIT_FWD(8, false);
-    else if (nw == 7) MMDIT_FWD(7, false);
-    else if (nw == 6) MMDIT_FWD(6, false);
-    else if (nw == 4) MMDIT_FWD(4, false);
-    else MMDIT_FWD(2, false);
-  }
-#endif
-#define MMDIT_FWD_DMA(NW, NS) hipLaunchKernelGGL((attn_fwd_dma_kernel<0, false, NW, NS>), dim3(((S + 32 * NW - 1) / (32 * NW)) * batch * heads), dim3(64 * NW), 0, s, (const bf16_t*)Q, \
-                                                (const bf16_t*)K, (const bf16_t*)V, batch * heads, heads, S, n_img, scale, (bf16_t*)Ox, (bf16_t*)Oc, lse)
-#ifdef MMDIT_PROBES                                   // experiments: waves per workgroup / ring depth of the DMA kernel (MMDIT_ATTN_FWD_GEO = 84 | 83 | 43 | 42 | 44)
-  else if (mmdit_exp_env("MMDIT_ATTN_FWD_GEO") && atoi(mmdit_exp_env("MMDIT_ATTN_FWD_GEO")) != 84) {
-    switch (atoi(mmdit_exp_env("MMDIT_ATTN_FWD_GEO"))) {
-      case 83: MMDIT_FWD_DMA(8, 3); break;
-      case 44: MMDIT_FWD_DMA(4, 4); break;
-      case 43: MMDIT_FWD_DMA(4, 3); break;
-      case 42: MMDIT_FWD_DMA(4, 2); break;
-      default: return MMDIT_ERR_ARG;
-    }
-  }
-#endif
-  else MMDIT_FWD_DMA(8, 4);
-#undef MMDIT_FWD_DMA
-#undef MMDIT_FWD
+  if (mode != 0 && mode != 1) return MMDIT_ERR_ARG;
+  if (mode == 1)                                     // the reference's rounding points (parity mode)
+    hipLaunchKernelGGL((attn_fwd_kernel<2, true>), dim3(((S + 63) / 64) * batch * heads), dim3(128), 0, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)V,
+                       batch * heads, heads, S, n_img, scale, (bf16_t*)Ox, (bf16_t*)Oc, lse);
+  else
+    hipLaunchKernelGGL((attn_fwd_dma_kernel<0, false, 8, 4>), dim3(((S + 255) / 256) * batch * heads), dim3(512), 0, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)V,
+                       batch * heads, heads, S, n_img, scale, (bf16_t*)Ox, (bf16_t*)Oc, lse);
   return mmdit_launch_status();
 }
 
@@ -1726,23 +1111,6 @@ extern "C" int mmdit_probe_attn_bwd_dkv_trace(const void* Q, const void* K, cons
 }
 #endif
 
-#ifdef MMDIT_PROBES
-// the same stamps for the de-phased kernel (plain epilogue): trace = 2048 workgroups x 8 waves x 72 slots
-extern "C" int mmdit_probe_attn_bwd_dkv_dp_trace(const void* Q, const void* K, const void* V, const void* dOx, const void* dOc, const float* lse, const float* delta,
-                                                 int batch, int heads, int S, int n_img, float scale, void* dK, void* dV, void* trace, mmdit_stream_t stream) {
-  static unsigned long long raised = 0;
-  if (!mmdit_device_once(raised)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_dp_kernel<bf16_t, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, dkv_lds_bytes<false>());
-    if (e != hipSuccess) return (int)e;
-    mmdit_device_mark(raised);
-  }
-  hipLaunchKernelGGL((attn_bwd_dkv_dp_kernel<bf16_t, false, true>), dim3(((S + 255) / 256) * batch * heads), dim3(512), dkv_lds_bytes<false>(), (hipStream_t)stream, (const bf16_t*)Q,
-                     (const bf16_t*)K, (const bf16_t*)V, (const bf16_t*)dOx, (const bf16_t*)dOc, lse, delta, batch * heads, heads, S, n_img, scale, (bf16_t*)dK, (bf16_t*)dV, QkFuse(),
-                     (unsigned long long*)trace);
-  return mmdit_launch_status();
-}
-#endif
-
 extern "C" int mmdit_attn_bwd_qk(const void* Q, const void* K, const void* V, const void* Ox, const void* Oc, const void* dOx, const void* dOc,
                                  const float* lse, float* delta, int batch, int heads, int S, int n_img, float scale,
                                  const void* qkv_x, const void* qkv_c, const float* wq_x, const float* wk_x, const float* wq_c, const float* wk_c,
@@ -1759,35 +1127,11 @@ extern "C" int mmdit_attn_bwd_qk(const void* Q, const void* K, const void* V, co
   if (!mmdit_device_once(raised)) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq_kernel<8, bf16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<8, bf16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-#ifdef MMDIT_PROBES
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_dp_kernel<bf16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, dkv_lds_bytes<true>());
-#endif
     if (e != hipSuccess) return (int)e;             // (positive: a HIP error code, as from mmdit_launch_status)
     mmdit_device_mark(raised);
   }
-#ifdef MMDIT_PROBES      // experiment (MMDIT_ATTN_ONEPASS=1): one pass per (batch, head), S <= 416 -- measured slower, see attn_bwd_onepass_kernel
-  if (S <= 32 * OP_MAXB && mmdit_exp_env("MMDIT_ATTN_ONEPASS") && atoi(mmdit_exp_env("MMDIT_ATTN_ONEPASS")) == 1) {
-    static unsigned long long raised1 = 0;
-    if (!mmdit_device_once(raised1)) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_onepass_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, OP_LDS);
-      if (e != hipSuccess) return (int)e;
-      mmdit_device_mark(raised1);
-    }
-    hipLaunchKernelGGL(attn_bwd_onepass_kernel, dim3(batch * heads), dim3(512), OP_LDS, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)V, (const bf16_t*)Ox,
-                       (const bf16_t*)Oc, (const bf16_t*)dOx, (const bf16_t*)dOc, lse, batch * heads, heads, S, n_img, scale, F,
-                       mmdit_exp_env("MMDIT_OP_DBG") ? atoi(mmdit_exp_env("MMDIT_OP_DBG")) : 0);
-    return mmdit_launch_status();
-  }
-#endif
   hipLaunchKernelGGL((attn_bwd_dq_kernel<8, bf16_t, true>), grid, dim3(512), lds, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)V, (const bf16_t*)Ox,
                      (const bf16_t*)Oc, (const bf16_t*)dOx, (const bf16_t*)dOc, lse, delta, batch * heads, heads, S, n_img, scale, (bf16_t*)nullptr, F);
-#ifdef MMDIT_PROBES      // experiment: the de-phased dK/dV kernel (MMDIT_ATTN_DKV_DP=1; needs a text output gradient when there are text tokens)
-  if (mmdit_exp_env("MMDIT_ATTN_DKV_DP") && atoi(mmdit_exp_env("MMDIT_ATTN_DKV_DP")) == 1 && (dOc || n_img == S)) {
-    hipLaunchKernelGGL((attn_bwd_dkv_dp_kernel<bf16_t, true>), grid, dim3(512), dkv_lds_bytes<true>(), s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)V, (const bf16_t*)dOx,
-                       (const bf16_t*)dOc, lse, delta, batch * heads, heads, S, n_img, scale, (bf16_t*)nullptr, (bf16_t*)nullptr, F);
-    return mmdit_launch_status();
-  }
-#endif
   hipLaunchKernelGGL((attn_bwd_dkv_kernel<8, bf16_t, true>), grid, dim3(512), lds, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)V, (const bf16_t*)dOx,
                      (const bf16_t*)dOc, lse, delta, batch * heads, heads, S, n_img, scale, (bf16_t*)nullptr, (bf16_t*)nullptr, F);
   return mmdit_launch_status();
@@ -1800,20 +1144,13 @@ extern "C" int mmdit_attn_bwd(const void* Q, const void* K, const void* V, const
   MMDIT_CHECK_ARG(Oc || n_img == S);
   hipStream_t s = (hipStream_t)stream;
   // (delta = rowsum(dO * O) is produced by the dQ kernel, which runs first)
-  const int nw = attn_waves(S);
 #define MMDIT_DKV(NW, TG) hipLaunchKernelGGL((attn_bwd_dkv_kernel<NW, TG>), dim3(((S + 32 * NW - 1) / (32 * NW)) * batch * heads), dim3(NW * 64), 0, s, (const bf16_t*)Q, (const bf16_t*)K, \
                                              (const bf16_t*)V, (const bf16_t*)dOx, (const bf16_t*)dOc, lse, delta, batch * heads, heads, S, n_img, scale, (TG*)dK, (TG*)dV)
 #define MMDIT_DQ(NW, TG) hipLaunchKernelGGL((attn_bwd_dq_kernel<NW, TG>), dim3(((S + 32 * NW - 1) / (32 * NW)) * batch * heads), dim3(NW * 64), 0, s, (const bf16_t*)Q, (const bf16_t*)K, \
                                             (const bf16_t*)V, (const bf16_t*)Ox, (const bf16_t*)Oc, (const bf16_t*)dOx, (const bf16_t*)dOc, lse, delta, batch * heads, heads, S, n_img, scale, (TG*)dQ)
   if (dq_dtype == MMDIT_BF16) {
-#ifdef MMDIT_PROBES      // experiments: other workgroup widths (MMDIT_ATTN_NW)
-    if (nw == 7) { MMDIT_DQ(7, bf16_t); MMDIT_DKV(7, bf16_t); }
-    else if (nw == 6) { MMDIT_DQ(6, bf16_t); MMDIT_DKV(6, bf16_t); }
-    else if (nw == 4) { MMDIT_DQ(4, bf16_t); MMDIT_DKV(4, bf16_t); }
-    else if (nw == 2) { MMDIT_DQ(2, bf16_t); MMDIT_DKV(2, bf16_t); }
-    else
-#endif
-    { MMDIT_DQ(8, bf16_t); MMDIT_DKV(8, bf16_t); }
+    MMDIT_DQ(8, bf16_t);
+    MMDIT_DKV(8, bf16_t);
   } else if (dq_dtype == MMDIT_F32) {
     MMDIT_DQ(2, float);
     MMDIT_DKV(2, float);

@@ -186,6 +186,7 @@ static inline int mmdit_launch_status() {
 
 // Experiment switches (tile configuration, schedule and ablation overrides of the GEMM / row kernels: the MMDIT_GEMM_* / MMDIT_QK_* variables of
 // tools/README.md) exist only in -DMMDIT_PROBES builds (tools/build_variant.sh); the product library has ONE path per launch.
+// They select between live kernels or tune them: the superseded kernels that such builds once carried were removed (last in commit a4c3a60).
 #include <stdlib.h>
 static inline const char* mmdit_exp_env(const char* name) {
 #ifdef MMDIT_PROBES

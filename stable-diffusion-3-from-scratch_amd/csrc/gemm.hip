@@ -249,7 +249,7 @@ int check_problem(const mmdit_gemm_args* a) {
 
 }  // namespace
 
-// workspace of the lean weight-gradient kernel's split tail (device memory owned by the caller; first 4 KiB: zero-initialised tickets)
+// workspace of the 8-phase weight-gradient kernel's split tail (device memory owned by the caller; first 4 KiB: zero-initialised tickets)
 // (one registration per DEVICE: the tickets and slots are device memory, and a ticket left non-zero by a launch on one GPU must not be
 //  seen by another)
 static void* g_ws[64] = {};
@@ -284,8 +284,6 @@ struct PlannerSwitches {
   bool kdec_streamk = false, kdec_plain = false;   // MMDIT_GEMM_KDEC=streamk / plain (see the K decomposition in choose_kernel)
   int tail_s = 0, debug = 0;     // MMDIT_GEMM_TAIL_S: force the tail's K split; MMDIT_GEMM_DEBUG: ablation bits (tools/gemm_ablate.py: 2 = operand stream only, 8 = no epilogue, 64 = no bf16 fast epilogue)
   int epi_direct = 0, raster = 8;   // MMDIT_GEMM_EPI=0; MMDIT_GEMM_RASTER: n-tiles per rasterization group (see locate_tile)
-  bool kk = true;                // MMDIT_GEMM_KK=0: the general kernel instead of the lean weight-gradient kernel
-  int p8 = 1;                    // MMDIT_GEMM_8P: 1 every lean launch on the 8-phase kernel; 2 only the 256x256 ones; 0 the round-2/3 kernels of gemm_lean.hip
 };
 #ifdef MMDIT_PROBES
 static const PlannerSwitches& planner_switches() {
@@ -293,10 +291,10 @@ static const PlannerSwitches& planner_switches() {
     PlannerSwitches w;
     auto num = [](const char* name, int& v) { if (const char* e = getenv(name)) v = atoi(e); };
     num("MMDIT_GEMM_CFG", w.cfg); num("MMDIT_GEMM_CFG_EPI", w.cfg_epi); num("MMDIT_GEMM_LEAN", w.lean); num("MMDIT_GEMM_TAIL_S", w.tail_s);
-    num("MMDIT_GEMM_DEBUG", w.debug); num("MMDIT_GEMM_RASTER", w.raster); num("MMDIT_GEMM_8P", w.p8);
+    num("MMDIT_GEMM_DEBUG", w.debug); num("MMDIT_GEMM_RASTER", w.raster);
     w.no_dma = getenv("MMDIT_GEMM_NO_DMA"); w.no_streamk = getenv("MMDIT_GEMM_NO_STREAMK"); w.no_persist = getenv("MMDIT_GEMM_NO_PERSIST");
-    int qk8 = 0, kk = 1;
-    num("MMDIT_QK_8PHASE", qk8); num("MMDIT_GEMM_KK", kk); w.qk8 = qk8 > 0; w.kk = kk != 0;
+    int qk8 = 0;
+    num("MMDIT_QK_8PHASE", qk8); w.qk8 = qk8 > 0;
     if (const char* e = getenv("MMDIT_GEMM_EPI")) w.epi_direct = atoi(e) == 0;
     if (const char* e = getenv("MMDIT_GEMM_KDEC")) { w.kdec_streamk = e[0] == 's'; w.kdec_plain = e[0] == 'p'; }
     return w;
@@ -330,7 +328,7 @@ static int pick_dma_cfg(const mmdit_gemm_args* args, int count, int split_k, boo
   const double r256 = mx8 ? 1.2 : args[0].a_dtype == MMDIT_FP8 ? 1.67 : 1.58;
   const double c128 = (double)((t128 * split_k + 2 * cu - 1) / (2 * cu)), c256 = r256 * (double)((t256 * split_k + cu - 1) / cu);
   if (lean_ok) {
-    // 320x256 tiles (lean kernel): a round costs 1.25x a 256x256 round (tile area); MMDiT-B's N = 768 GEMMs at batch 64 fit ONE round
+    // 320x256 tiles (lean launches): a round costs 1.25x a 256x256 round (tile area); MMDiT-B's N = 768 GEMMs at batch 64 fit ONE round
     long t320 = 0;
     for (int i = 0; i < count; i++) t320 += (long)((args[i].M + 319) / 320) * ((args[i].N + 255) / 256);
     const double c320 = 1.25 * 1.58 * (double)((t320 + cu - 1) / cu);
@@ -351,9 +349,9 @@ struct QkRequest {
 
 // One launch, decided before anything runs (plan_gemm; no launch, no writes to library state) and run by launch_plan.  mmdit_gemm_plan and
 // mmdit_gemm_zero_mask report from the same plan the launch runs.
-// Kernel families: the register-staged kernel of this file, the LDS-DMA kernel (gemm_dma.hip), the wide-slot lean kernel (gemm_lean.hip; in probe builds
-// also the other lean kernels), the round-3 weight-gradient kernel (probe builds), the 8-phase kernel (gemm8p.hip) and its implicit-GEMM convolution.
-enum GemmKernel { KERNEL_REG, KERNEL_DMA, KERNEL_WIDE, KERNEL_KK, KERNEL_8P, KERNEL_8P_CONV };
+// Kernel families: the register-staged kernel of this file, the LDS-DMA kernel (gemm_dma.hip), the wide-slot kernel (gemm_lean.hip: the QKV launch
+// at 320 rows), the 8-phase kernel (gemm8p.hip) and its implicit-GEMM convolution.
+enum GemmKernel { KERNEL_REG, KERNEL_DMA, KERNEL_WIDE, KERNEL_8P, KERNEL_8P_CONV };
 struct GemmPlan {
   GroupParams gp;
   GemmKernel kernel;
@@ -408,7 +406,7 @@ static int choose_kernel(const mmdit_gemm_args* args, int count, const QkRequest
   int bm = BM, bn = BN, cfg = CFG_128x128;
   // stream-K for the weight gradients (k-major A): fp32 C must be pre-zeroed by the caller (a0->stream_k)
   const bool stream_k = dma && !sw.no_streamk && a0->stream_k && a0->c_dtype == MMDIT_F32 && split_k == 1 && a0->act == MMDIT_ACT_NONE && !a0->accumulate;
-  // lean hot-path kernel (gemm_lean.hip): bf16 row-major A, bf16 output, bias / SiLU epilogue only
+  // lean hot-path launches (the 8-phase kernel of gemm8p.hip; the QKV launch at 320 rows: gemm_lean.hip): bf16 row-major A, bf16 output, bias / SiLU epilogue only
   bool lean_ok = dma && sw.lean > 0 && !fp8 && !conv && !stream_k && split_k == 1 && !a0->a_kmajor && a0->c_dtype == MMDIT_BF16 &&
                  (a0->act == MMDIT_ACT_NONE || a0->act == MMDIT_ACT_SILU || swiglu || swiglu_bwd) && !a0->accumulate;
   for (int i = 0; i < count && lean_ok; i++) {
@@ -517,20 +515,20 @@ static int choose_kernel(const mmdit_gemm_args* args, int count, const QkRequest
     MMDIT_CHECK_ARG(dma && a0->c_dtype == MMDIT_F32 && a0->act == MMDIT_ACT_NONE && !a0->accumulate && split_k <= 64);
     for (int i = 0; i < count; i++) MMDIT_CHECK_ARG(!args[i].aux && !args[i].gate);
   }
-  // lean weight-gradient kernel (gemm_lean.hip, gemm_kk_kernel): both operands k-major, fp32 C, 256x256 tiles, the round + tail (or
-  // caller-split) schedule, nothing but store / accumulate / atomic add in the epilogue.  MMDIT_GEMM_KK=0: the general kernel.
-  bool kk = dma && sw.kk && !fp8 && !conv && !gp.stream_k && cfg == CFG_256x256 && a0->a_kmajor && a0->b_kmajor &&
+  // eligible for the 8-phase weight-gradient instantiation (gemm8_kernel<256, true, true, float>): both operands k-major, fp32 C, 256x256 tiles, the
+  // round + tail (or caller-split) schedule, nothing but store / accumulate / atomic add in the epilogue.  Anything else: the general kernel.
+  bool wgrad8 = dma && !fp8 && !conv && !gp.stream_k && cfg == CFG_256x256 && a0->a_kmajor && a0->b_kmajor &&
             a0->c_dtype == MMDIT_F32 && a0->act == MMDIT_ACT_NONE;
-  for (int i = 0; i < count && kk; i++) {
+  for (int i = 0; i < count && wgrad8; i++) {
     const mmdit_gemm_args* a = &args[i];
-    kk = !a->bias && !a->gate && !a->residual && !a->aux && a->N % 4 == 0 && a->ldc % 4 == 0 && aligned16(a->C);
+    wgrad8 = !a->bias && !a->gate && !a->residual && !a->aux && a->N % 4 == 0 && a->ldc % 4 == 0 && aligned16(a->C);
   }
   // ... whose split tail goes through the registered workspace (mmdit_gemm_set_workspace) instead of fp32 atomics when it is large enough:
   // 4 KiB of tickets + one 256x256 fp32 slot per (tail tile, K slice)
   gp.ws_slots = nullptr; gp.ws_count = nullptr; gp.sched = nullptr;
   gp.qk_on = 0; gp.qkQ = gp.qkK = gp.qkV = nullptr; gp.qk_heads = 0; gp.qk_s_total = 0;
   if (qkr) {
-    // the fused QKV epilogue exists in the wide-slot lean kernel only, for one or two streams in the caller's order, [q | k | v] columns
+    // the fused QKV epilogue exists in the wide-slot kernel (gemm_lean.hip) only, for one or two streams in the caller's order, [q | k | v] columns
     // (round 5: ... and, for MX e4m3 operands, in the 8-phase kernel at 256 rows)
     const bool mxqk = dma && fp8 && gp.mx && cfg == CFG_256x256 && !a0->a_kmajor && a0->c_dtype == MMDIT_BF16;
     if (!(lean || mxqk) || count > 2 || a0->act != MMDIT_ACT_NONE || a0->b_kmajor) return MMDIT_ERR_SHAPE;
@@ -547,7 +545,7 @@ static int choose_kernel(const mmdit_gemm_args* args, int count, const QkRequest
     gp.qk_on = 1; gp.qk_heads = qkr->heads; gp.qk_s_total = qkr->s_total;
     gp.qkQ = (bf16_t*)qkr->Q; gp.qkK = (bf16_t*)qkr->K; gp.qkV = (bf16_t*)qkr->V;
   }
-  if (kk && gp.split_k > 1) {
+  if (wgrad8 && gp.split_k > 1) {
     const long long tail_tiles = tiles - full_tiles;
     if (ds.ws && tail_tiles <= 1024 && 8192 + tail_tiles * gp.split_k * 65536LL * 4 <= ds.ws_bytes) {
       gp.ws_count = (int*)ds.ws;
@@ -561,20 +559,20 @@ static int choose_kernel(const mmdit_gemm_args* args, int count, const QkRequest
     const Problem& q = gp.p[i];
     if (dma && !gp.ws_slots && (gp.stream_k || (gp.split_k > 1 && q.tile_start + q.tiles_m * q.tiles_n > gp.full_tiles))) pl->zero_mask |= 1u << order[i];
   }
-  // the 8-phase kernel (gemm8p.hip) takes every 256x256 launch of the lean kernels (MMDIT_GEMM_8P=0: the round-2/3 kernels of gemm_lean.hip)
+  // the 8-phase kernel (gemm8p.hip) takes every lean launch and every eligible weight gradient
   // (the QKV launch with the QK-norm / RoPE epilogue stays on the wide kernel at 320 rows: with that epilogue's registers the 320-row 8-phase
   //  variant measured slower, 1.73 vs 1.59 ms per step)
   // e4m3 operands (E8M0 block scales or per-tensor scales) on the 8-phase loop: 256 x 256 tiles, bf16 output (bias allowed) or the SwiGLU epilogue (bf16 or MX output)
-  bool mx8 = sw.p8 > 0 && dma && fp8 && cfg == CFG_256x256 && (!qkr || gp.mx) && !stream_k && split_k == 1 && (a0->act == MMDIT_ACT_NONE || swiglu) && !a0->accumulate;
+  bool mx8 = dma && fp8 && cfg == CFG_256x256 && (!qkr || gp.mx) && !stream_k && split_k == 1 && (a0->act == MMDIT_ACT_NONE || swiglu) && !a0->accumulate;
   for (int i = 0; i < count && mx8; i++) {
     const mmdit_gemm_args* a = &args[i];
     mx8 = (a->c_dtype == MMDIT_BF16 || (swiglu && a->c_dtype == MMDIT_FP8)) && (!a->aux || (swiglu && a->c_dtype == MMDIT_BF16)) && !a->gate && !a->residual && a->K % 128 == 0 &&
           a->N % 8 == 0 && a->ldc % 8 == 0 && aligned16(a->C) && (int64_t)a->M * a->lda < (1ll << 32) && (int64_t)a->N * a->ldb < (1ll << 32);
   }
-  const bool p8 = mx8 || (sw.p8 > 0 && ((kk && cfg == CFG_256x256) || (lean && (cfg == CFG_256x256 || (cfg == CFG_320x256 && sw.p8 == 1 && !qkr)))));
+  const bool p8 = mx8 || wgrad8 || (lean && (cfg == CFG_256x256 || (cfg == CFG_320x256 && !qkr)));
   // implicit-GEMM convolutions on the 8-phase loop (round 5): 256 x 256 tiles, every problem a convolution with C % 64 == 0, bf16 output (bias) or fp32 output
   // (bias + residual), nothing else in the epilogue
-  bool conv8 = sw.p8 > 0 && conv && dma && !fp8 && cfg == CFG_256x256 && !stream_k && split_k == 1 && a0->act == MMDIT_ACT_NONE && !a0->accumulate &&
+  bool conv8 = conv && dma && !fp8 && cfg == CFG_256x256 && !stream_k && split_k == 1 && a0->act == MMDIT_ACT_NONE && !a0->accumulate &&
                (a0->c_dtype == MMDIT_BF16 || a0->c_dtype == MMDIT_F32);
   for (int i = 0; i < count && conv8; i++) {
     const mmdit_gemm_args* a = &args[i];
@@ -582,10 +580,10 @@ static int choose_kernel(const mmdit_gemm_args* args, int count, const QkRequest
             (!a->residual || (a->ld_res % 4 == 0 && aligned16(a->residual))) && (!a->bias || aligned16(a->bias));
   }
   if (swiglu_bwd && !p8) return MMDIT_ERR_SHAPE;
-  pl->kernel = conv8 ? KERNEL_8P_CONV : p8 ? KERNEL_8P : lean ? KERNEL_WIDE : kk ? KERNEL_KK : dma ? KERNEL_DMA : KERNEL_REG;
+  pl->kernel = conv8 ? KERNEL_8P_CONV : p8 ? KERNEL_8P : lean ? KERNEL_WIDE : dma ? KERNEL_DMA : KERNEL_REG;
   pl->cfg = cfg; pl->mx8 = mx8;
-  // (128 with k-major A: the lean weight-gradient kernel)
-  pl->code = dma ? (cfg | (gp.stream_k ? 16 : 0) | (tail_mode ? 32 : 0) | (lean || kk ? 128 : 0) | (p8 || conv8 ? 256 : 0)) : 64;
+  // (128 with k-major A: the 8-phase weight-gradient instantiation)
+  pl->code = dma ? (cfg | (gp.stream_k ? 16 : 0) | (tail_mode ? 32 : 0) | (lean || wgrad8 ? 128 : 0) | (p8 || conv8 ? 256 : 0)) : 64;
   // a persistent launch of the 8-phase kernel with 256-row tiles and more positions than the budget's workgroups CLAIMS its tiles when claiming is on
   // and the workspace is registered (gemm8p.hip); e4m3-operand and convolution launches, and the statically balanced tail, keep the static walk
   const bool claimed = pl->kernel == KERNEL_8P && !mx8 && cfg == CFG_256x256 && gp.persistent && gp.tail_first < 0 && total_work(gp) > pl->cu;
@@ -674,7 +672,6 @@ static int launch_plan(const GemmPlan& pl, hipStream_t s) {
     case KERNEL_8P_CONV: return launch_gemm8_conv(pl.c_dt == MMDIT_F32, *gp, s, pl.cu);
     case KERNEL_8P: return launch_gemm8(pl.cfg, pl.a_km, pl.b_km, *gp, s, pl.cu, pl.ktail, pl.mx8);
     case KERNEL_WIDE: return launch_lean_cfg(pl.cfg, pl.b_km, *gp, s, pl.cu);
-    case KERNEL_KK: return launch_lean_wgrad(*gp, s, pl.cu);
     case KERNEL_DMA: return launch_dma(pl.cfg, pl.a_km, pl.b_km, pl.c_dt, pl.aux_dt, pl.fp8, *gp, s, pl.cu);
     case KERNEL_REG:
       if (pl.precision == MMDIT_PREC_BF16 && pl.a_dt == MMDIT_BF16 && pl.b_dt == MMDIT_BF16) return dispatch_out<bf16_t, bf16_t, false>(pl.c_dt, pl.aux_dt, pl.a_km, pl.b_km, *gp, s);

@@ -646,6 +646,8 @@ __device__ __forceinline__ void epi8_f32_slot(AccT<MT>& acc, float* slot, int wm
       for (int it = 0; it < 4; it++) {
         const int r = it * 8 + rr;
         const f32x4 t = *LDS_PTR(const f32x4, stage + r * 128 + ((rc ^ (r & 7)) << 4));
+        // device-scope write-through store (sc1): the slot is read by a workgroup on another XCD, whose L2 is not coherent with this one;
+        // a release FENCE would write back this XCD's whole L2 instead (measured: the fenced version was slower than the atomics)
         float* dst = slot + (int64_t)(wm * (MT / 2) + i * 32 + r) * 256 + wn * 64 + j * 32 + rc * 4;
         asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst), "v"(t) : "memory");
       }
@@ -696,7 +698,9 @@ __global__ __launch_bounds__(512) void gemm8_kernel(GroupParams gp) {
   const bool hiw = wave + 8 * (PAW - 1) < GE::PA;      // (wave-uniform) this wave carries PAW A pieces per half-tile, the others PAW - 1
 
   int pos = (int)blockIdx.x, end = total_work(gp);
-  if (gp.tail_first >= 0) {   // balanced tail: this workgroup's share of the tail units (gemm_lean.hip gemm_kk_kernel)
+  // balanced tail (planned in gemm.hip choose_kernel: one full round whose short-K tiles finish early): the tail units go to the E = tail_G - tail_first
+  // workgroups whose first tile is a short one, round robin; a workgroup whose first tile is a long one gets none (its walk ends after the full round)
+  if (gp.tail_first >= 0) {
     const int e = xcd_chunk((int)blockIdx.x, gp.full_tiles) - gp.tail_first, E = gp.tail_G - gp.tail_first;
     const int left = (gp.total_tiles - gp.full_tiles) * gp.split_k - e;
     end = gp.full_tiles + (e < 0 || left <= 0 ? 0 : (left + E - 1) / E) * gp.tail_G;
@@ -1237,18 +1241,22 @@ __global__ __launch_bounds__(512) void gemm8_kernel(GroupParams gp) {
   else if constexpr (EPI == EPI_F32R) epi8_f32r<MT>(acc, q, m0, n0, wr, wc, lane, stage);
   else {
     if (it.atomic && gp.ws_slots) {
-      // partial tile of the split tail through the workspace (gemm_lean.hip gemm_kk_kernel: slot store, ticket, the last slice sums)
+      // Partial tile of the split tail: no fp32 atomics (each 256x256 partial costs ~0.6 us of L2 atomic throughput for the WHOLE launch).
+      // Store it to the slice's workspace slot, publish (write-through stores landed + ticket); the last of the tile's slices to arrive sums
+      // the slots in slice order -- deterministic -- and writes C.  No workgroup ever waits for another one.
       constexpr int TE = 256 * 256, NW = 8;
       const int tt = it.tile - gp.full_tiles, S = gp.split_k;
       float* slots = gp.ws_slots + (int64_t)tt * S * TE;
       epi8_f32_slot<MT>(acc, slots + (int64_t)it.sk * TE, wr, wc, lane, stage);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the write-through stores of this wave have reached memory
+      __syncthreads();                                   // ... of every wave
+      if (tid == 0) *s_ticket = atomicAdd(gp.ws_count + tt, 1);   // (device-scope atomic, performed at the memory side)
       __syncthreads();
-      if (tid == 0) *s_ticket = atomicAdd(gp.ws_count + tt, 1);
-      __syncthreads();
-      if (*s_ticket == S - 1) {
+      if (*s_ticket == S - 1) {               // (workgroup-uniform) every slice of this tile has been published
         float* C = (float*)q.C;
-        constexpr int NCH = TE / 4 / (64 * NW);
+        // device-scope (sc1) loads past this XCD's L2, 4 chunks x up to 4 slices in flight per lane; the loads are issued from asm (the
+        // compiler has no sc1 load), so their destinations are handed to it only through the wait that follows them
+        constexpr int NCH = TE / 4 / (64 * NW);     // 16-byte chunks per lane (32 for the 256x256 tile)
 #pragma unroll 1
         for (int b0 = 0; b0 < NCH; b0 += 4) {
           f32x4 tsum[4];
@@ -1285,9 +1293,9 @@ __global__ __launch_bounds__(512) void gemm8_kernel(GroupParams gp) {
             }
           }
         }
-        if (tid == 0) gp.ws_count[tt] = 0;
+        if (tid == 0) gp.ws_count[tt] = 0;   // ready for the next launch (stream order)
       }
-      __syncthreads();
+      __syncthreads();                       // (the ticket word is reused by the next partial tile of this workgroup)
     } else {
       epi8_f32<MT>(acc, q, m0, n0, wr, wc, lane, stage, it.atomic, gp.accumulate != 0);
     }

@@ -252,14 +252,13 @@ __device__ __forceinline__ void epilogue_direct(const f32x16 (&acc)[MI][NJ], con
 
 
 // tile configurations of the LDS-DMA kernel (gemm_dma.hip)
-enum DmaCfg { CFG_128x128 = 0, CFG_256x128 = 1, CFG_256x256 = 2, CFG_320x256 = 3 };   // 320x256: lean kernel only (gemm_lean.hip)
+enum DmaCfg { CFG_128x128 = 0, CFG_256x128 = 1, CFG_256x256 = 2, CFG_320x256 = 3 };   // 320x256: lean launches only (gemm8p.hip; the QKV launch: gemm_lean.hip)
 inline void dma_cfg_tile(int cfg, int& bm, int& bn) { bm = cfg == CFG_128x128 ? 128 : cfg == CFG_320x256 ? 320 : 256; bn = cfg >= CFG_256x256 ? 256 : 128; }
 // Launchers: `cu` = the compute units the plan was made for (persistent grids); gp.sched = the claimed launch's scheduler slot (gemm.hip launch_plan)
 int launch_dma(int cfg, bool a_km, bool b_km, int c_dtype, int aux_dtype, bool fp8, const GroupParams& gp, hipStream_t s, int cu);
-// lean hot-path kernel: bf16 row-major A, bf16 B (row- or k-major), bf16 C, bias / SiLU only; cfg CFG_256x256 or CFG_320x256
+// gemm_lean.hip: the wide-slot kernel, QKV launch only (gp.qk_on, CFG_320x256, row-major B, no activation); anything else is MMDIT_ERR_SHAPE
 int launch_lean_cfg(int cfg, bool b_km, const GroupParams& gp, hipStream_t s, int cu);
-int launch_lean_wgrad(const GroupParams& gp, hipStream_t s, int cu);   // gemm_lean.hip: k-major x k-major -> fp32, 256x256, K-decomposed schedule
-// gemm8p.hip: the de-phased 8-phase main loop on 256x256 tiles (16x16x32 MFMA): every launch the lean kernels take at that tile size
+// gemm8p.hip: the de-phased 8-phase main loop on 256x256 tiles (16x16x32 MFMA): every other lean launch and the weight gradients
 int launch_gemm8_fp8(bool b_km, const GroupParams& gp, hipStream_t s, int cu);       // gemm8p_inf.hip: e4m3 operands (gp.mx: E8M0 block scales, else per-tensor), 256x256 tiles
 int launch_gemm8_conv(bool f32_out, const GroupParams& gp, hipStream_t s, int cu);   // gemm8p.hip CONV: implicit-GEMM 3x3 convolution, 256x256 tiles, bf16 (+ bias) or fp32 (+ bias + residual) output
 int launch_gemm8(int cfg, bool a_km, bool b_km, const GroupParams& gp, hipStream_t s, int cu, bool ktail, bool fp8);   // ktail: some weight-gradient K is not a multiple of 64   // cfg: CFG_256x256 / CFG_320x256 (bf16 outputs only)

@@ -174,11 +174,8 @@ def _variant(arr, n, outs):
     if plan & 256:      # the 8-phase kernel (csrc/gemm8p.hip): <a_kmajor, b_kmajor, epilogue>
         epi = "f32" if a.a_kmajor else "swiglu" if a.act == ACT_SWIGLU else "swiglu_bwd" if a.act == ACT_SWIGLU_BWD else "bf16"
         return f"gemm8_kernel<{320 if plan & 15 == 3 else 256},{km},{epi}>" + ("+ktail" if plan & 32 else "")
-    if plan & 128 and a.a_kmajor:
-        return "gemm_kk_kernel<2,4,4,2>" + ("+ktail" if plan & 32 else "")
     if plan & 128:
-        kern = "gemm_lean_kernel" if _lib.experiment("MMDIT_GEMM_WIDE", "1") == "0" else "gemm_wide_kernel"
-        return f"{kern}<{_CFG[plan & 15]},{int(bool(a.b_kmajor))}>" + ("+swiglu" if a.act == ACT_SWIGLU else "")
+        return f"gemm_wide_kernel<{_CFG[plan & 15]},{int(bool(a.b_kmajor))}>" + ("+swiglu" if a.act == ACT_SWIGLU else "")
     return f"gemm_dma_kernel<{_CFG[plan & 15]},{km},{tc},{ta}>" + ("+streamK" if plan & 16 else "") + ("+ktail" if plan & 32 else "") + ("+swiglu" if a.act == ACT_SWIGLU else "")
 
 

@@ -564,7 +564,7 @@ def test_attention_oracle_mode_matches_cpu_oracle(ops):
 
 @pytest.mark.parametrize("kmajor", [False, True])
 def test_gemm_lean_kernel_320x256_and_256x256(ops, kmajor):
-    """The lean hot-path kernel (csrc/gemm_lean.hip) on the shapes it is chosen for: image + text rows grouped, N = 768 (320x256 tiles:
+    """The lean hot-path launches (the 8-phase kernel, csrc/gemm8p.hip: gemm8_kernel<320 | 256, ...>) on the shapes they are chosen for: image + text rows grouped, N = 768 (320x256 tiles:
     one round; ragged last row tiles 16384 = 51.2 x 320, 9856 = 30.8 x 320) and N = 2304, forward (row-major weight, bias + SiLU) and
     data-gradient (k-major weight) layouts, against torch on the same bf16 operands (fp32 accumulate; bf16 output rounding 4e-3)."""
     if os.environ.get("MMDIT_GEMM_LEAN") == "0":
@@ -715,10 +715,10 @@ def test_gemm_qkv_epilogue_on_mx_operands_equals_gemm_plus_row_kernel(ops, Bt, H
 
 
 def test_gemm_lean_weight_gradient_kernel(ops):
-    """gemm_kk_kernel (csrc/gemm_lean.hip: both operands k-major, fp32 out, 256x256 tiles) on the schedules it runs: whole-K rounds
+    """The 8-phase weight-gradient kernel (csrc/gemm8p.hip, gemm8_kernel<256, true, true, f32>: both operands k-major, fp32 out, 256x256 tiles) on the schedules it runs: whole-K rounds
     only, rounds + a split tail (atomic partial tiles into the pre-zeroed output), the balanced tail of a block's mixed image + text
     launch, a caller-requested split-K, accumulation into an existing gradient, and ragged M / N edges -- against fp64 references of the
-    same bf16 operands, and against the general kernel (MMDIT_GEMM_KK=0 is read once per process, so that comparison is the reference)."""
+    same bf16 operands."""
     def make(shapes, seed, **kw):
         probs, refs = [], []
         for i, (rows, M, N) in enumerate(shapes):
@@ -733,8 +733,6 @@ def test_gemm_lean_weight_gradient_kernel(ops):
             ops._fill_gemm(arr[i], **p)
         return ops._lib.lib().mmdit_gemm_plan(arr, len(probs))
 
-    if os.environ.get("MMDIT_GEMM_KK") == "0":
-        pytest.skip("the lean weight-gradient kernel is switched off (MMDIT_GEMM_KK=0)")
     # (a) a block-like group: 4 "image" + 4 "text" problems, 288 tiles of 256x256 -> one round + balanced split tail
     shapes = [(4096, 2304, 768), (2432, 2304, 768), (4096, 768, 768), (2432, 768, 768), (4096, 6144, 768), (2432, 6144, 768), (4096, 768, 3072), (2432, 768, 3072)]
     probs, refs = make(shapes, 100, stream_k=True)

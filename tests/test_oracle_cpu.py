@@ -225,6 +225,9 @@ def test_library_exports_every_declared_symbol():
     L = ctypes.CDLL(_lib.LIB_PATH)
     for s in declared:
         assert hasattr(L, s), s
+    # the measurement entry points exist in -DMMDIT_PROBES builds only (the third one left the sources with its kernel)
+    for s in ("mmdit_probe_attn_fwd_dbg", "mmdit_probe_attn_bwd_dkv_trace", "mmdit_probe_attn_bwd_dkv_dp_trace"):
+        assert not hasattr(L, s), s
     assert _lib.lib().mmdit_abi_version() == _lib.ABI_VERSION == 10 and _lib.lib().mmdit_struct_size(0) == ctypes.sizeof(_lib.GemmArgs) and _lib.lib().mmdit_build_arch() == b"gfx950"
 
 

@@ -80,7 +80,7 @@ if E4M3:
 (Ox, Oc, lse), tf = timed(lambda: ops.attn_fwd(Q, K, V, N, scale, 0))
 (dQ, dK, dV), tb = timed(lambda: ops.attn_bwd(Q, K, V, Ox, Oc, dOx, dOc, lse, N, scale, torch.bfloat16))
 fl = 4.0 * B * H * S * S * hd
-print(f"attn fwd {tf * 1e6:8.1f} us  {fl / tf / 1e12:7.1f} TF   bwd {tb * 1e6:8.1f} us  {2.5 * fl / tb / 1e12:7.1f} TF   (NW={os.environ.get('MMDIT_ATTN_NW', '2')})")
+print(f"attn fwd {tf * 1e6:8.1f} us  {fl / tf / 1e12:7.1f} TF   bwd {tb * 1e6:8.1f} us  {2.5 * fl / tb / 1e12:7.1f} TF")
 
 # reference on a slice of the batch (fp32 math on the bf16 inputs)
 nb = 4
