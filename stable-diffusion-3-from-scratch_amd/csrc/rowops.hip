@@ -215,7 +215,7 @@ __device__ __forceinline__ void ln_mod_bwd_body(int block, const TG* __restrict_
       }
     }
   }
-  if constexpr (NIT <= 6) {
+  if constexpr (NIT <= 6) {      // (restated as ln_bwd_flush in tests/test_rowops_edges_gpu.py)
     // combine the 4 waves in LDS (one quantity at a time: <= 24 KB), then one atomic per column per block
     __shared__ float red[4][NIT * 256];
     auto flush = [&](const float (&v)[NIT][4], float* dst) {
@@ -1031,7 +1031,7 @@ __global__ __launch_bounds__(256) void time_embed_bwd_kernel(const TG* __restric
   if (threadIdx.x == 0) atomicAdd(dts, (red[0] + red[1] + red[2] + red[3]) * t[b]);
 }
 
-inline int nit_for(int d) { return (d / 4 + 63) / 64; }
+inline int nit_for(int d) { return (d / 4 + 63) / 64; }      // (restated, with the NIT_SWITCH buckets, in tests/test_rowops_edges_gpu.py)
 inline int grid_cap(int64_t n, int bs) { int64_t g = (n + bs - 1) / bs; return (int)(g < 1 ? 1 : g > 4096 ? 4096 : g); }
 
 }  // namespace
@@ -1129,6 +1129,7 @@ extern "C" int mmdit_gate_residual_fwd(const float* x, const void* acc, int acc_
 // keep LN_BWD_RCH)
 // (generalised: the smallest multiple of 4 rows -- one row per wave and step -- for which the launch fits the chip in ONE round; the resident
 //  workgroups per CU follow from the kernel's registers: 4 up to d = 768, 3 at d = 1024, 2 above)
+// (restated as ln_bwd_rch in tests/test_rowops_edges_gpu.py)
 static int ln_bwd_one_round_rch(const mmdit_ln_bwd_problem* a, const mmdit_ln_bwd_problem* b, int d, int dout_dtype, bool gated) {
   auto wgs = [&](int r) { return (long)(a->rows / a->rows_per_batch) * ((a->rows_per_batch + r - 1) / r) + (long)(b->rows / b->rows_per_batch) * ((b->rows_per_batch + r - 1) / r); };
   const int nit_ = nit_for(d), nit_abs = nit_ < 0 ? -nit_ : nit_;
@@ -1242,14 +1243,14 @@ extern "C" int mmdit_text_rmsnorm_bwd(const void* dout1, const void* dout2, int 
 // Launch shape of the QK-norm/RoPE backward: RL row lanes per workgroup (as many as fit 1024 threads; every workgroup ends with 128
 // global atomics on the same two cache lines, so fewer, fatter workgroups), `lanes` rows in flight per iteration pair, a multiple of the
 // tokens per sample when RoPE applies (same token for all rows of a lane: factors loaded once).
-static int qk_bwd_rl(int heads, int min_rows) {
+static int qk_bwd_rl(int heads, int min_rows) {      // (restated in tests/test_rowops_edges_gpu.py)
   static const int env = [] { const char* e = mmdit_exp_env("MMDIT_QK_RL"); return e ? atoi(e) : 0; }();
   int rl = 1024 / (24 * heads);
   if (env > 0 && env < rl) rl = env;
   if (rl < 1 || min_rows < 2048) rl = 1;
   return rl;
 }
-static int qk_bwd_grid(int rows, int tokens, bool rope, int& rl) {
+static int qk_bwd_grid(int rows, int tokens, bool rope, int& rl) {      // (restated in tests/test_rowops_edges_gpu.py)
   static const int lanes_max = [] { const char* e = mmdit_exp_env("MMDIT_QK_LANES"); return e ? atoi(e) : 768; }();
   if (rl == 1) {
     int g = rows < 512 ? rows : 512;
@@ -1304,7 +1305,7 @@ extern "C" int mmdit_qk_norm_rope_fwd(const mmdit_qk_problem* probs, int count, 
   if (int e = qk_list(probs, count, batch, heads, s_total, 1024, false, false, nullptr, nullptr, nullptr, q)) return e;
   if (qkv_dtype != MMDIT_BF16 && qkv_dtype != MMDIT_F32) return MMDIT_ERR_DTYPE;
   int g[2] = {0, 0};
-  for (int i = 0; i < count; i++) {
+  for (int i = 0; i < count; i++) {      // (grid and same_token restated as qk_fwd_path in tests/test_rowops_edges_gpu.py)
     g[i] = q[i].rows < 1024 ? q[i].rows : 1024;
     if (q[i].rcos && q[i].tokens <= 1024 && q[i].rows >= q[i].tokens) g[i] = (g[i] / q[i].tokens > 0 ? g[i] / q[i].tokens : 1) * q[i].tokens;
   }
@@ -1323,7 +1324,7 @@ extern "C" int mmdit_qk_norm_rope_bwd(const mmdit_qk_problem* probs, int count, 
   if (combo < 0) return MMDIT_ERR_DTYPE;
   int rl = qk_bwd_rl(heads, count == 2 && q[1].rows < q[0].rows ? q[1].rows : q[0].rows);     // (one block shape for every problem of the list)
   int g[2] = {0, 0};
-  bool fast = true;
+  bool fast = true;      // (restated as qk_bwd_path in tests/test_rowops_edges_gpu.py)
   for (int i = 0; i < count; i++) {
     g[i] = qk_bwd_grid(q[i].rows, q[i].tokens, q[i].rcos != nullptr, rl);
     fast = fast && (!q[i].rcos || (g[i] * rl) % q[i].tokens == 0);
@@ -1497,7 +1498,7 @@ extern "C" int mmdit_colsum(const void* x, int dtype, int rows, int cols, int64_
   hipStream_t s = (hipStream_t)stream;
   // few rows (the per-sample partial sums of a block: 64 x 2d): 8-row chunks, so that the loads of a thread are all in flight at once --
   // the 64-row chunk walked them as one latency-bound loop in two workgroups (10-17 us for 400 KB)
-  const int rch = rows <= 256 ? 8 : CO_RCH;
+  const int rch = rows <= 256 ? 8 : CO_RCH;      // (restated as colsum_rch in tests/test_rowops_edges_gpu.py)
   dim3 grid((cols + 1023) / 1024, (rows + rch - 1) / rch);
   if (dtype == MMDIT_BF16) hipLaunchKernelGGL((colsum_kernel<bf16_t>), grid, dim3(256), 0, s, (const bf16_t*)x, rows, cols, ld, out, rch);
   else if (dtype == MMDIT_F32) hipLaunchKernelGGL((colsum_kernel<float>), grid, dim3(256), 0, s, (const float*)x, rows, cols, ld, out, rch);
