@@ -17,6 +17,7 @@ def experiment(name: str, default: str) -> str:
 LIB_PATH = os.environ.get("MMDIT_LIB") or os.path.join(_HERE, "libmmdit_hip.so")   # MMDIT_LIB: A/B a scratch build
 HEADER_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip.h")
 HEADER_EXT_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_ext.h")   # opt-in entry points outside the versioned core ABI
+HEADER_HD128_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_hd128.h")   # the head-width-128 entry points, outside it as well
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_SILU, ACT_SWIGLU, ACT_SWIGLU_BWD = 0, 1, 2, 3
@@ -143,6 +144,16 @@ _EXT_SIGNATURES = {
     "mmdit_attn_fwd_e4m3": ([_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp], _i),
 }
 ATTN_E4M3_KEY_TILE, ATTN_E4M3_QUERY_TILE = 64, 128   # MMDIT_ATTN_E4M3_KEY_TILE / MMDIT_ATTN_E4M3_QUERY_TILE
+# entry points of include/mmdit_hip_hd128.h: the argument lists of their 64-wide namesakes in the core table
+_HD128_SIGNATURES = {
+    "mmdit_attn_fwd_hd128": _SIGNATURES["mmdit_attn_fwd"],
+    "mmdit_attn_bwd_hd128": _SIGNATURES["mmdit_attn_bwd"],
+    "mmdit_qk_norm_rope_fwd_hd128": _SIGNATURES["mmdit_qk_norm_rope_fwd"],
+    "mmdit_qk_norm_rope_bwd_hd128": _SIGNATURES["mmdit_qk_norm_rope_bwd"],
+}
+ATTN_HD128_KEY_TILE, ATTN_HD128_QUERY_TILE = 32, 128   # MMDIT_ATTN_HD128_KEY_TILE / MMDIT_ATTN_HD128_QUERY_TILE
+QK_HD128_MAX_HEADS, QK_HD128_RL_MIN_ROWS = 21, 2048    # MMDIT_QK_HD128_MAX_HEADS / MMDIT_QK_HD128_RL_MIN_ROWS
+HEAD_DIMS = (64, 128)                                  # head widths the attention and QK-norm / RoPE kernels are built for
 ADAMW_CHUNK = 65536   # MMDIT_ADAMW_CHUNK
 ABI_VERSION = 10      # MMDIT_ABI_VERSION of include/mmdit_hip.h this binding mirrors
 # struct ids of mmdit_struct_size() -> ctypes mirrors (None: laid out with numpy record dtypes in optim.py / ops.py: 48 / 24 bytes)
@@ -166,6 +177,13 @@ def declared_ext_symbols():
     return sorted(set(re.findall(r"\b(mmdit_[a-z0-9_]+)\s*\(", txt)) - {"mmdit_stream_t"})
 
 
+def declared_hd128_symbols():
+    """Entry points declared by include/mmdit_hip_hd128.h (parsed the same way)."""
+    with open(HEADER_HD128_PATH) as f:
+        txt = f.read()
+    return sorted(set(re.findall(r"\b(mmdit_[a-z0-9_]+)\s*\(", txt)) - {"mmdit_stream_t"})
+
+
 def lib():
     """Load the HIP library (once).  Raises RuntimeError if it is not built."""
     global _lib
@@ -183,7 +201,7 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        for name, (argtypes, restype) in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()):
+        for name, (argtypes, restype) in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_HD128_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError -> symbol missing: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

@@ -3,13 +3,14 @@ configuration (dual stream, attn_type softmax / softmax_flash, RoPE2d, non-causa
 forward 118-135, 174-194, 258-293, 410-425).  Experimental attention types of the reference
 (cosine*, relu, silu, exp, both, qk_half_dim, 1-D RoPE, RoPE2dV2) are out of scope and
 raise.  kv_merge_attn (243-251) is implemented: the keys / values of adjacent token pairs of each stream are
-averaged (mmdit_qk_norm_rope_fwd_merge) and S queries attend to S / 2 keys (mmdit_attn_fwd_kv)."""
+averaged (mmdit_qk_norm_rope_fwd_merge) and S queries attend to S / 2 keys (mmdit_attn_fwd_kv).
+Head width dim / num_heads: 64 (every fused and e4m3 form) or 128 (the plain kernels of include/mmdit_hip_hd128.h; no kv_merge_attn)."""
 from types import SimpleNamespace as NS
 
 import torch
 from torch import nn
 
-from .. import engine, ops
+from .. import _lib, engine, ops
 from ..packing import Pack
 from .rotary_embedding import RotaryEmbedding
 
@@ -27,7 +28,7 @@ class _AttentionFn(torch.autograd.Function):
         xa, ca = m.act(x.reshape(B * N, d).contiguous()), m.act(c.reshape(B * Mt, d).contiguous())
         qkv_x = ops.gemm(xa, w.Wqkv_x, out_dtype=m.T, precision=m.prec)
         qkv_c = ops.gemm(ca, w.Wqkv_c, out_dtype=m.T, precision=m.prec)
-        Q = torch.empty((B, H, S, 64), dtype=BF16, device=dev)
+        Q = torch.empty((B, H, S, mod.head_dim), dtype=BF16, device=dev)
         if mod.kv_merge_attn:
             mod._check_even(N, Mt)
             K, V = torch.empty((B, H, S // 2, 64), dtype=BF16, device=dev), torch.empty((B, H, S // 2, 64), dtype=BF16, device=dev)
@@ -66,7 +67,7 @@ class _AttentionFn(torch.autograd.Function):
             dac = m.act(doc.reshape(B * Mt, d).contiguous())
             dOc = ops.gemm(dac, w.Wo_c, b_kmajor=True, out_dtype=BF16, precision=m.prec)
             mod._po_c.split_grad(ops.gemm(dac, Oca, a_kmajor=True, b_kmajor=True, out_dtype=F32, precision=m.prec), gout)
-        gq_x, gk_x, gq_c, gk_c = [torch.zeros(64, dtype=F32, device=dev) for _ in range(4)]
+        gq_x, gk_x, gq_c, gk_c = [torch.zeros(mod.head_dim, dtype=F32, device=dev) for _ in range(4)]
         if mod.kv_merge_attn:
             dQ, dK, dV = ops.attn_bwd(Q, K, V, Ox, Oc, dOx, dOc, lse, N, mod.scale, m.T, s_kv=S // 2)
             dqkv_x, dqkv_c = ops.qk_norm_rope_bwd_merge_pair(dQ, dK, dV, (qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], N, 0, gq_x, gk_x),
@@ -94,8 +95,11 @@ class Attention(nn.Module):
             raise RuntimeError("Attention: only the dual-stream, non-causal configuration of the trained model is implemented")
         if positional_encoding != "RoPE2d":
             raise RuntimeError("Attention: only positional_encoding='RoPE2d' is implemented")
-        if dim // num_heads != 64 or dim % num_heads:
-            raise RuntimeError("Attention: head_dim must be 64 (the reference's dim = 64*num_heads convention, train.py:37-39)")
+        if dim % num_heads or dim // num_heads not in _lib.HEAD_DIMS:
+            raise RuntimeError(f"Attention: head_dim = dim / num_heads must be 64 (the reference's dim = 64*num_heads convention, train.py:37-39) or 128, "
+                               f"the widths the attention kernels are built for, but got dim={dim}, num_heads={num_heads}")
+        if kv_merge_attn and dim // num_heads != 64:
+            raise RuntimeError("Attention: kv_merge_attn is built for head_dim 64 only (the pair-averaging kernels mmdit_qk_norm_rope_*_merge / mmdit_attn_*_kv are 64 wide)")
         self.positional_encoding, self.kv_merge_attn, self.RoPE_Scale = positional_encoding, kv_merge_attn, RoPE_Scale
         self.layer_idx, self.dual, self.last = layer_idx, dual, last
         self.query_proj_x = nn.Linear(dim, dim, bias=False)
@@ -139,7 +143,7 @@ class Attention(nn.Module):
         return NS(Wqkv_x=self._pqkv_x.get(m), Wqkv_c=self._pqkv_c.get(m), Wo_x=self._po_x.get(m),
                   Wo_c=None if self.last else self._po_c.get(m),
                   wq_x=self.q_norm_x.weight.detach(), wk_x=self.k_norm_x.weight.detach(),
-                  wq_c=self.q_norm_c.weight.detach(), wk_c=self.k_norm_c.weight.detach(), kv_merge=bool(self.kv_merge_attn))
+                  wq_c=self.q_norm_c.weight.detach(), wk_c=self.k_norm_c.weight.detach(), kv_merge=bool(self.kv_merge_attn), hd=self.head_dim)
 
     def scatter_grads(self, g, out: dict):
         self._pqkv_x.split_grad(g.Wqkv_x, out)

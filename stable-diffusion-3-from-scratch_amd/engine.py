@@ -344,7 +344,10 @@ def block_fwd(m, w, X, C, y, dims, rope, cond=None, keep=True, lazy=False):
            and w.mlp_x.hidden % 128 == 0 and (w.last or (not w.mlp_c.gelu and w.mlp_c.hidden % 128 == 0)) and _MX_FUSE)
 
     (sv.X, sv.ln1x, sv.mu1x, sv.rs1x), (sv.C, sv.ln1c, sv.mu1c, sv.rs1c) = _norm_pair(m, (X, ms.scale1x, ms.shift1x, N), (C, ms.scale1c, ms.shift1c, Mt), mx=mxf)
-    sv.Q = torch.empty((B, H, S, 64), dtype=BF16, device=dev)
+    hd = w.hd      # head width: 64, or 128 (the unfused route below: no QKV epilogue, no fused QK backward, no e4m3 / MX forms)
+    if hd != 64 and m.fp8:
+        raise RuntimeError(f"head width {hd}: no fp8 / mxfp8 path (the e4m3 GEMM epilogues and attention kernels are built for head width 64)")      # (direct engine use; diff_model.set_precision refuses it first)
+    sv.Q = torch.empty((B, H, S, hd), dtype=BF16, device=dev)
     # kv_merge_attn (Attention.py:243-251): the keys / values of adjacent token pairs are averaged -- K / V have S / 2 rows.  A GEMM epilogue sees
     # one token per row, so the plain grouped QKV GEMM and the merging norm / RoPE kernel run instead of the fused launch
     merge = w.kv_merge
@@ -352,11 +355,13 @@ def block_fwd(m, w, X, C, y, dims, rope, cond=None, keep=True, lazy=False):
         assert N % 2 == 0 and Mt % 2 == 0, "Merge attention requires an even number of keys"
         if m.fp8:
             raise RuntimeError("kv_merge_attn: no fp8 / mxfp8 path")      # (direct engine use; diff_model.set_precision refuses the combination with the full message)
+        if hd != 64:
+            raise RuntimeError(f"kv_merge_attn: head width {hd} is not built (the pair-averaging kernels are 64 wide)")      # (direct engine use; Attention refuses it at construction)
         sv.K, sv.V = torch.empty((B, H, S // 2, 64), dtype=BF16, device=dev), torch.empty((B, H, S // 2, 64), dtype=BF16, device=dev)
     else:
         sv.K, sv.V = torch.empty_like(sv.Q), torch.empty_like(sv.Q)
     fused = None
-    if not merge and _QKV_FUSE and m.fast and dev.type == "cuda" and m.T == BF16 and (not m.fp8 or mxf) and d == H * 64:
+    if not merge and _QKV_FUSE and m.fast and dev.type == "cuda" and m.T == BF16 and (not m.fp8 or mxf) and hd == 64:
         # QK-norm + RoPE + joint-layout store in the QKV GEMM's epilogue (one launch, no second pass over the raw projection); None: the
         # planner would not give these problems to a kernel with that epilogue (bf16: the lean wide-slot kernel; MX operands: the 8-phase kernel)
         qp = [dict(A=sv.ln1x, B=w.Wqkv_x, out_dtype=m.T, precision=m.prec), dict(A=sv.ln1c, B=w.Wqkv_c, out_dtype=m.T, precision=m.prec)]
@@ -387,7 +392,7 @@ def block_fwd(m, w, X, C, y, dims, rope, cond=None, keep=True, lazy=False):
         if both:
             sv.Oca = sv.Oc.view(B * Mt, d)
     else:
-        sv.Ox, sv.Oc, sv.lse = ops.attn_fwd(sv.Q, sv.K, sv.V, N, 64 ** -0.5, m.attn_mode, s_kv=S // 2 if merge else None)
+        sv.Ox, sv.Oc, sv.lse = ops.attn_fwd(sv.Q, sv.K, sv.V, N, hd ** -0.5, m.attn_mode, s_kv=S // 2 if merge else None)
         sv.Oxa = m.act(sv.Ox.view(B * N, d))
         if both:
             sv.Oca = m.act(sv.Oc.view(B * Mt, d))
@@ -465,10 +470,10 @@ def _qk_bwd_two_pass(m, w, sv, g, dOx, dOc, dims, rope, dev):
     B, N, Mt, H, d = dims
     S = N + Mt
     if w.kv_merge:      # S queries, S / 2 pair-averaged keys: dK / dV come back merged and are halved onto both tokens of a pair
-        dQ, dK, dV = ops.attn_bwd(sv.Q, sv.K, sv.V, sv.Ox, sv.Oc, dOx, dOc, sv.lse, N, 64 ** -0.5, m.T, s_kv=S // 2)
+        dQ, dK, dV = ops.attn_bwd(sv.Q, sv.K, sv.V, sv.Ox, sv.Oc, dOx, dOc, sv.lse, N, w.hd ** -0.5, m.T, s_kv=S // 2)
         return ops.qk_norm_rope_bwd_merge_pair(dQ, dK, dV, (sv.qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], N, 0, g.wq_x, g.wk_x),
                                                (sv.qkv_c, w.wq_c, w.wk_c, None, None, Mt, N, g.wq_c, g.wk_c), B, H, S, m.T)
-    dQ, dK, dV = ops.attn_bwd(sv.Q, sv.K, sv.V, sv.Ox, sv.Oc, dOx, dOc, sv.lse, N, 64 ** -0.5, m.T)
+    dQ, dK, dV = ops.attn_bwd(sv.Q, sv.K, sv.V, sv.Ox, sv.Oc, dOx, dOc, sv.lse, N, w.hd ** -0.5, m.T)
     if _LN_PAIR and dev.type == "cuda":
         return ops.qk_norm_rope_bwd_pair(dQ, dK, dV, (sv.qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], N, 0, g.wq_x, g.wk_x),
                                          (sv.qkv_c, w.wq_c, w.wk_c, None, None, Mt, N, g.wq_c, g.wk_c), B, H, S, m.T)
@@ -490,7 +495,7 @@ def block_bwd_begin(m, w, sv, dims, dev, defer_cond=False):
     hx = sv.gu_x.shape[1]
     nb = 2 if both else 1
     # parameter gradients first (they form one flat sub-arena a reducer can average in place), scratch after them
-    shapes = [(nb * d,), (hx,), (64,), (64,), (64,), (64,)] + ([(sv.gu_c.shape[1],)] if both else []) + ([] if defer_cond else [(d,)])
+    shapes = [(nb * d,), (hx,), (w.hd,), (w.hd,), (w.hd,), (w.hd,)] + ([(sv.gu_c.shape[1],)] if both else []) + ([] if defer_cond else [(d,)])
     npar = len(shapes)
     shapes += [tuple(sv.mod.shape), (B, nb * d)]
     zs, small_arena = _zeros_views(shapes, dev, prefix=npar)
@@ -595,7 +600,7 @@ def block_bwd(m, w, sv, dX2, dC2, dy_acc, dims, rope, defer_cond=False, st=None,
 
     # ---- attention core + QK norm / RoPE
     # the QK-norm + RoPE backward runs in the epilogues of the attention backward kernels (ops.attn_bwd_qk) when the shapes allow it:
-    # no dQ / dK / dV round trip, one pass less (MMDIT_ATTN_QK_FUSE=0: the two-pass form)
+    # no dQ / dK / dV round trip, one pass less (MMDIT_ATTN_QK_FUSE=0: the two-pass form).  Head width 64 only (attn_bwd_qk_ok): the literals below are its
     if not w.kv_merge and _QK_FUSE and m.fast and dev.type == "cuda" and ops.attn_bwd_qk_ok(sv.Q, N, sv.qkv_x) and g.wq_x.data_ptr() + 768 == g.wk_c.data_ptr():
         dqkv_x, dqkv_c = ops.attn_bwd_qk(sv.Q, sv.K, sv.V, sv.Ox, sv.Oc, dOx, dOc, sv.lse, N, 64 ** -0.5, sv.qkv_x, sv.qkv_c, w.wq_x, w.wk_x, w.wq_c, w.wk_c,
                                          rope[0], rope[1], torch.as_strided(g.wq_x, (256,), (1,)))

@@ -60,7 +60,7 @@ class _MMDiTFn(torch.autograd.Function):
 
 class diff_model(nn.Module):
     # inCh - number of latent channels; class_dim - pooled text embedding width; patch_size - 2;
-    # dim / hidden_scale / num_heads / num_blocks - transformer geometry (dim = 64*num_heads);
+    # dim / hidden_scale / num_heads / num_blocks - transformer geometry (dim = 64*num_heads, or 128*num_heads);
     # attn_type - "softmax" | "softmax_flash"; MLP_type - "swiglu" | "gelu"; positional_encoding - "RoPE2d"
     def __init__(self, inCh, class_dim, patch_size, dim, hidden_scale, num_heads, attn_type, MLP_type, num_blocks, device, positional_encoding,
                  max_res_orig=256, max_res=256, update_max_res=False, kv_merge_attn=False, qk_half_dim=False, text_loss=False,
@@ -162,6 +162,9 @@ class diff_model(nn.Module):
         assert precision in ("fast", "parity", "fp8", "mxfp8")
         if precision in ("fp8", "mxfp8") and self.kv_merge_attn:
             raise RuntimeError(f"set_precision('{precision}'): kv_merge_attn has no e4m3 path (mmdit_attn_fwd_mx keeps one sequence length); use 'fast' or 'parity'")
+        if precision in ("fp8", "mxfp8") and self.dim // self.num_heads != 64:
+            raise RuntimeError(f"set_precision('{precision}'): head width {self.dim // self.num_heads} has no e4m3 path (the QKV epilogue, mmdit_attn_fwd_mx and "
+                               "mmdit_attn_fwd_e4m3 are built for head width 64); use 'fast' or 'parity'")
         if attention not in ("bf16", "e4m3"):
             raise ValueError(f"set_precision: attention must be 'bf16' or 'e4m3', got {attention!r}")
         if attention == "e4m3" and precision not in ("fp8", "mxfp8"):

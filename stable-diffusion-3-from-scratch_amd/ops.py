@@ -608,6 +608,30 @@ def text_rmsnorm_bwd(dout1, dout2, x, w1, w2, s1, s2, split):
     return dw1, dw2, ds1, ds2
 
 
+def _head_dim(t, what="attention"):
+    """Head width of a (batch, heads, S, head_dim) operand: 64 (the core entry points) or 128 (the *_hd128 ones of include/mmdit_hip_hd128.h)."""
+    hd = t.shape[-1]
+    if hd not in _lib.HEAD_DIMS:
+        raise RuntimeError(f"{what} kernels are built for head_dim 64 (the reference's dim = 64*num_heads convention) and 128, got {hd}")
+    return hd
+
+
+def _qk_hd128(fn, streams, heads, bwd):
+    """The 128-wide entry point of a plain QK-norm + RoPE launch (the kv_merge forms are 64 wide), after checking that the rows, norm weights,
+    RoPE tables and weight-gradient accumulators follow the head width the kernel indexes them by."""
+    if fn not in ("mmdit_qk_norm_rope_fwd", "mmdit_qk_norm_rope_bwd"):
+        raise RuntimeError(f"{fn}: built for head_dim 64 only")
+    if heads > _lib.QK_HD128_MAX_HEADS:
+        raise RuntimeError(f"{fn}_hd128: at most {_lib.QK_HD128_MAX_HEADS} heads (a qkv row is one workgroup of 48 * heads threads), got {heads}")
+    for st in streams:
+        if st[0].shape[-1] != 3 * heads * 128 or st[1].numel() != 128 or st[2].numel() != 128 or (st[3] is not None and st[3].shape[-1] != 128):
+            raise RuntimeError(f"{fn}_hd128: qkv rows are 3 * heads * 128 wide, norm weights 128, RoPE tables (tokens, 128); got {tuple(st[0].shape)}, "
+                               f"{st[1].numel()}, {st[2].numel()}, {None if st[3] is None else tuple(st[3].shape)}")
+        if bwd and (st[7].numel() != 128 or st[8].numel() != 128):
+            raise RuntimeError(f"{fn}_hd128: dwq / dwk are 128 floats")
+    return fn + "_hd128"
+
+
 def _qk(fn, streams, batch, heads, s_total, T3, out_dtype=None, status=check):
     """One launch of the QK-norm + RoPE entry point `fn` over a list of 1 or 2 streams = (qkv, wq, wk, rope_cos, rope_sin, tokens, tok0) and, for the
     backward entry points (out_dtype given), + (dwq, dwk), which are ADDED to.  T3 = the joint (Q, K, V) written by a forward, the
@@ -621,6 +645,8 @@ def _qk(fn, streams, batch, heads, s_total, T3, out_dtype=None, status=check):
             q.dqkv, q.dwq, q.dwk = _p(dqkv), _p(st[7]), _p(st[8])
             outs.append(dqkv)
     a, b, c = (_p(t) for t in T3)
+    if _head_dim(T3[0], "QK-norm / RoPE") == 128:
+        fn = _qk_hd128(fn, streams, heads, out_dtype is not None)
     launch, qkv_dt = getattr(_lib.lib(), fn), _dt(streams[0][0])
     if out_dtype is None:
         status(launch(probs, len(streams), qkv_dt, batch, heads, s_total, a, b, c, _s()), fn)
@@ -689,18 +715,29 @@ def _kv_operands(Q, K, V, s_kv):
         _c(t)
 
 
+def _plain_operands(Q, K, V):
+    """Checks of the 128-wide launches: three contiguous bf16 operands of one shape."""
+    for t in (Q, K, V):
+        if t.dtype != torch.bfloat16 or t.shape != Q.shape:
+            raise RuntimeError(f"attention operands are bfloat16 of one shape (batch, heads, S, head_dim), got {t.dtype} {tuple(t.shape)}")
+        _c(t)
+
+
 def attn_fwd(Q, K, V, n_img, scale, mode, s_kv=None):
     """s_kv (kv_merge_attn, Attention.py:243-251): K and V are (batch, heads, s_kv, 64), 1 <= s_kv <= S; None = the plain launch."""
     batch, heads, S, hd = Q.shape
-    if hd != 64:
-        raise RuntimeError("attention kernels are built for head_dim 64 (the reference's dim = 64*num_heads convention)")
+    _head_dim(Q)
     D = heads * hd
     Ox = torch.empty((batch, n_img, D), dtype=torch.bfloat16, device=Q.device)
     Oc = torch.empty((batch, S - n_img, D), dtype=torch.bfloat16, device=Q.device) if S > n_img else None
     lse = torch.empty((batch, heads, S), dtype=torch.float32, device=Q.device)
     if s_kv is not None:
-        _kv_operands(Q, K, V, s_kv)
+        _kv_operands(Q, K, V, s_kv)      # (64 wide only)
         check(_lib.lib().mmdit_attn_fwd_kv(_p(Q), _p(K), _p(V), batch, heads, S, int(s_kv), n_img, float(scale), mode, _p(Ox), _p(Oc), _p(lse), _s()), "mmdit_attn_fwd_kv")
+        return Ox, Oc, lse
+    if hd == 128:
+        _plain_operands(Q, K, V)
+        check(_lib.lib().mmdit_attn_fwd_hd128(_p(Q), _p(K), _p(V), batch, heads, S, n_img, float(scale), mode, _p(Ox), _p(Oc), _p(lse), _s()), "mmdit_attn_fwd_hd128")
         return Ox, Oc, lse
     check(_lib.lib().mmdit_attn_fwd(_p(Q), _p(K), _p(V), batch, heads, S, n_img, float(scale), mode, _p(Ox), _p(Oc), _p(lse), _s()), "mmdit_attn_fwd")
     return Ox, Oc, lse
@@ -708,6 +745,7 @@ def attn_fwd(Q, K, V, n_img, scale, mode, s_kv=None):
 
 def attn_bwd(Q, K, V, Ox, Oc, dOx, dOc, lse, n_img, scale, out_dtype, s_kv=None):
     batch, heads, S, hd = Q.shape
+    _head_dim(Q)
     delta = torch.empty((batch, heads, S), dtype=torch.float32, device=Q.device)
     dQ = torch.empty(Q.shape, dtype=out_dtype, device=Q.device)
     if s_kv is not None:      # dK / dV follow K / V: (batch, heads, s_kv, 64)
@@ -719,6 +757,11 @@ def attn_bwd(Q, K, V, Ox, Oc, dOx, dOc, lse, n_img, scale, out_dtype, s_kv=None)
         return dQ, dK, dV
     dK = torch.empty(Q.shape, dtype=out_dtype, device=Q.device)
     dV = torch.empty(Q.shape, dtype=out_dtype, device=Q.device)
+    if hd == 128:
+        _plain_operands(Q, K, V)
+        check(_lib.lib().mmdit_attn_bwd_hd128(_p(Q), _p(K), _p(V), _p(_c(Ox)), _p(_c(Oc)), _p(_c(dOx)), _p(_c(dOc)), _p(_c(lse)), _p(delta), batch, heads, S, n_img,
+                                              float(scale), _p(dQ), _p(dK), _p(dV), _dt(dQ), _s()), "mmdit_attn_bwd_hd128")
+        return dQ, dK, dV
     check(_lib.lib().mmdit_attn_bwd(_p(Q), _p(K), _p(V), _p(Ox), _p(Oc), _p(_c(dOx)), _p(_c(dOc)), _p(lse), _p(delta), batch, heads, S, n_img,
                                     float(scale), _p(dQ), _p(dK), _p(dV), _dt(dQ), _s()), "mmdit_attn_bwd")
     return dQ, dK, dV

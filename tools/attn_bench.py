@@ -3,7 +3,10 @@ Times forward and backward (prep + dQ + dK/dV launches) with HIP events; checks 
 python tools/attn_bench.py [reps]
 python tools/attn_bench.py --e4m3 [--out=FILE] [reps [B H N M]]: the forward of the e4m3 inference modes instead -- mmdit_attn_fwd_e4m3 (bf16 and MX
 outputs) beside mmdit_attn_fwd mode 0 and mmdit_attn_fwd_mx, by default at the sampler's MMDiT-L shape (batch 16, 16 heads, 1024 image + 154 text
-tokens); the kernels alternate inside every round, the table gives median and min / max over the rounds and is appended to FILE."""
+tokens); the kernels alternate inside every round, the table gives median and min / max over the rounds and is appended to FILE.
+python tools/attn_bench.py --hd128 [--out=FILE] [reps [B H N M]]: forward (mode 0) and backward (bf16 gradients) of the 128-wide kernels (mmdit_attn_fwd_hd128 /
+mmdit_attn_bwd_hd128) at B x H x 128 beside the 64-wide kernels at B x 2H x 64 -- the same d and the same FLOPs; default batch 16, 8 heads x 128 against
+16 x 64, 1024 image + 154 text tokens.  Same table as --e4m3."""
 import os
 import sys
 
@@ -14,10 +17,11 @@ import sd3_amd  # noqa: E402,F401
 from sd3_amd import ops  # noqa: E402
 
 E4M3 = "--e4m3" in sys.argv
+HD128 = "--hd128" in sys.argv
 OUT = next((a.split("=", 1)[1] for a in sys.argv if a.startswith("--out=")), None)
 sys.argv = [a for a in sys.argv if not a.startswith("--")]
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-B, H, N, M, hd = (16, 16, 1024, 154, 64) if E4M3 else (64, 12, 256, 154, 64)
+B, H, N, M, hd = (16, 16, 1024, 154, 64) if E4M3 else (16, 8, 1024, 154, 128) if HD128 else (64, 12, 256, 154, 64)
 if len(sys.argv) > 5:      # python tools/attn_bench.py reps B H N M   (e.g. 20 16 16 1024 154: MMDiT-L 512^2 batch 16)
     B, H, N, M = (int(v) for v in sys.argv[2:6])
 S = N + M
@@ -73,8 +77,43 @@ def e4m3_table(rounds=7):
             f.write("\n".join(lines) + "\n")
 
 
+def hd128_table(rounds=7):
+    """The 128-wide kernels at (B, H, S, 128) and the 64-wide ones at (B, 2 H, S, 64), alternating inside each round."""
+    import platform
+    import statistics
+    import time
+    Q6, K6, V6 = rnd(B, 2 * H, S, 64), rnd(B, 2 * H, S, 64), rnd(B, 2 * H, S, 64)
+    f128, f64 = ops.attn_fwd(Q, K, V, N, scale, 0), ops.attn_fwd(Q6, K6, V6, N, 0.125, 0)
+    kernels = [(f"mmdit_attn_fwd mode 0        {2 * H:>3} x  64", 1.0, lambda: ops.attn_fwd(Q6, K6, V6, N, 0.125, 0)),
+               (f"mmdit_attn_fwd_hd128 mode 0  {H:>3} x 128", 1.0, lambda: ops.attn_fwd(Q, K, V, N, scale, 0)),
+               (f"mmdit_attn_bwd -> bf16       {2 * H:>3} x  64", 2.5, lambda: ops.attn_bwd(Q6, K6, V6, f64[0], f64[1], dOx, dOc, f64[2], N, 0.125, torch.bfloat16)),
+               (f"mmdit_attn_bwd_hd128 -> bf16 {H:>3} x 128", 2.5, lambda: ops.attn_bwd(Q, K, V, f128[0], f128[1], dOx, dOc, f128[2], N, scale, torch.bfloat16))]
+    t = {name: [] for name, _, _ in kernels}
+    for _ in range(rounds):
+        for name, _, fn in kernels:
+            t[name].append(timed(fn)[1] * 1e6)
+    fl = 4.0 * B * H * S * S * hd
+    lines = [f"{time.strftime('%Y-%m-%d %H:%M')}  {torch.cuda.get_device_name(0)} ({platform.node()})  attention, B={B} S={S} (n_img={N}) d={H * hd}, "
+             f"{rounds} rounds x {reps} launches per kernel, HIP events; the 64-wide kernels are the parent commit's (csrc/attention.hip is unchanged)",
+             f"{'kernel':<46} {'median us':>10} {'min':>8} {'max':>8} {'TF (median)':>12}"]
+    for name, mult, _ in kernels:
+        med = statistics.median(t[name])
+        lines.append(f"{name:<46} {med:10.1f} {min(t[name]):8.1f} {max(t[name]):8.1f} {mult * fl / med / 1e6:12.1f}")
+    nb = min(B, 2)
+    ref = torch.softmax(Q[:nb].float() @ K[:nb].float().transpose(-1, -2) * scale, dim=-1) @ V[:nb].float()
+    o = torch.cat([f128[0][:nb].view(nb, N, H, hd), f128[1][:nb].view(nb, M, H, hd)], 1).permute(0, 2, 1, 3).float()
+    lines.append(f"rel-L2 of O (128 wide) against fp32 attention: {float((o - ref).norm() / ref.norm()):.2e}")
+    print("\n".join(lines))
+    if OUT:
+        with open(OUT, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 if E4M3:
     e4m3_table()
+    sys.exit(0)
+if HD128:
+    hd128_table()
     sys.exit(0)
 
 (Ox, Oc, lse), tf = timed(lambda: ops.attn_fwd(Q, K, V, N, scale, 0))
