@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("MMDIT_LIB") or os.path.join(_HERE, "libmmdit_hip.so")
 HEADER_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip.h")
 HEADER_EXT_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_ext.h")   # opt-in entry points outside the versioned core ABI
 HEADER_HD128_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_hd128.h")   # the head-width-128 entry points, outside it as well
+HEADER_ROPE3_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_rope3.h")   # the RoPE2dV2 entry points, outside it as well
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_SILU, ACT_SWIGLU, ACT_SWIGLU_BWD = 0, 1, 2, 3
@@ -153,6 +154,12 @@ _HD128_SIGNATURES = {
 }
 ATTN_HD128_KEY_TILE, ATTN_HD128_QUERY_TILE = 32, 128   # MMDIT_ATTN_HD128_KEY_TILE / MMDIT_ATTN_HD128_QUERY_TILE
 QK_HD128_MAX_HEADS, QK_HD128_RL_MIN_ROWS = 21, 2048    # MMDIT_QK_HD128_MAX_HEADS / MMDIT_QK_HD128_RL_MIN_ROWS
+# entry points of include/mmdit_hip_rope3.h (positional_encoding="RoPE2dV2"): the argument lists of the plain QK-norm / RoPE launches with
+# head_dim after heads
+_ROPE3_SIGNATURES = {
+    "mmdit_qk_norm_rope3_fwd": ([ctypes.POINTER(QkProblem), _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "mmdit_qk_norm_rope3_bwd": ([ctypes.POINTER(QkProblem), _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
+}
 HEAD_DIMS = (64, 128)                                  # head widths the attention and QK-norm / RoPE kernels are built for
 ADAMW_CHUNK = 65536   # MMDIT_ADAMW_CHUNK
 ABI_VERSION = 10      # MMDIT_ABI_VERSION of include/mmdit_hip.h this binding mirrors
@@ -184,6 +191,13 @@ def declared_hd128_symbols():
     return sorted(set(re.findall(r"\b(mmdit_[a-z0-9_]+)\s*\(", txt)) - {"mmdit_stream_t"})
 
 
+def declared_rope3_symbols():
+    """Entry points declared by include/mmdit_hip_rope3.h (parsed the same way)."""
+    with open(HEADER_ROPE3_PATH) as f:
+        txt = f.read()
+    return sorted(set(re.findall(r"\b(mmdit_[a-z0-9_]+)\s*\(", txt)) - {"mmdit_stream_t"})
+
+
 def lib():
     """Load the HIP library (once).  Raises RuntimeError if it is not built."""
     global _lib
@@ -201,7 +215,7 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        for name, (argtypes, restype) in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_HD128_SIGNATURES.items()):
+        for name, (argtypes, restype) in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_HD128_SIGNATURES.items()) + list(_ROPE3_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError -> symbol missing: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

@@ -1,8 +1,9 @@
 """Joint image+text attention: mirror of the reference's src/blocks/Attention.py for the trained
-configuration (dual stream, attn_type softmax / softmax_flash, RoPE2d, non-causal; ctor 16-114,
-forward 118-135, 174-194, 258-293, 410-425).  Experimental attention types of the reference
-(cosine*, relu, silu, exp, both, qk_half_dim, 1-D RoPE, RoPE2dV2) are out of scope and
-raise.  kv_merge_attn (243-251) is implemented: the keys / values of adjacent token pairs of each stream are
+configuration (dual stream, attn_type softmax / softmax_flash, RoPE2d or RoPE2dV2, non-causal; ctor 16-114,
+forward 118-135, 174-194, 220-239, 258-293, 410-425).  Experimental attention types of the reference
+(cosine*, relu, silu, exp, both, qk_half_dim, 1-D RoPE) are out of scope and
+raise.  positional_encoding="RoPE2dV2" (rotary_embedding_2d_v2.RoPE2D: channel triples rotated by a row and a column angle) runs on the unfused
+route: plain QKV GEMM, mmdit_qk_norm_rope3_fwd / _bwd (include/mmdit_hip_rope3.h), attention; no kv_merge_attn, no fp8 / mxfp8.  kv_merge_attn (243-251) is implemented: the keys / values of adjacent token pairs of each stream are
 averaged (mmdit_qk_norm_rope_fwd_merge) and S queries attend to S / 2 keys (mmdit_attn_fwd_kv).
 Head width dim / num_heads: 64 (every fused and e4m3 form) or 128 (the plain kernels of include/mmdit_hip_hd128.h; no kv_merge_attn)."""
 from types import SimpleNamespace as NS
@@ -13,6 +14,7 @@ from torch import nn
 from .. import _lib, engine, ops
 from ..packing import Pack
 from .rotary_embedding import RotaryEmbedding
+from .rotary_embedding_2d_v2 import RoPE2D
 
 F32, BF16 = torch.float32, torch.bfloat16
 
@@ -29,7 +31,12 @@ class _AttentionFn(torch.autograd.Function):
         qkv_x = ops.gemm(xa, w.Wqkv_x, out_dtype=m.T, precision=m.prec)
         qkv_c = ops.gemm(ca, w.Wqkv_c, out_dtype=m.T, precision=m.prec)
         Q = torch.empty((B, H, S, mod.head_dim), dtype=BF16, device=dev)
-        if mod.kv_merge_attn:
+        if mod.rope3:
+            K, V = torch.empty_like(Q), torch.empty_like(Q)
+            ops.qk_norm_rope3_fwd(qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], B, N, H, S, 0, Q, K, V)
+            ops.qk_norm_rope3_fwd(qkv_c, w.wq_c, w.wk_c, None, None, B, Mt, H, S, N, Q, K, V)
+            Ox, Oc, lse = ops.attn_fwd(Q, K, V, N, mod.scale, m.attn_mode)
+        elif mod.kv_merge_attn:
             mod._check_even(N, Mt)
             K, V = torch.empty((B, H, S // 2, 64), dtype=BF16, device=dev), torch.empty((B, H, S // 2, 64), dtype=BF16, device=dev)
             ops.qk_norm_rope_fwd_merge_pair((qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], N, 0), (qkv_c, w.wq_c, w.wk_c, None, None, Mt, N), B, H, S, Q, K, V)
@@ -68,7 +75,11 @@ class _AttentionFn(torch.autograd.Function):
             dOc = ops.gemm(dac, w.Wo_c, b_kmajor=True, out_dtype=BF16, precision=m.prec)
             mod._po_c.split_grad(ops.gemm(dac, Oca, a_kmajor=True, b_kmajor=True, out_dtype=F32, precision=m.prec), gout)
         gq_x, gk_x, gq_c, gk_c = [torch.zeros(mod.head_dim, dtype=F32, device=dev) for _ in range(4)]
-        if mod.kv_merge_attn:
+        if mod.rope3:
+            dQ, dK, dV = ops.attn_bwd(Q, K, V, Ox, Oc, dOx, dOc, lse, N, mod.scale, m.T)
+            dqkv_x = ops.qk_norm_rope3_bwd(dQ, dK, dV, qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], B, N, H, S, 0, gq_x, gk_x, m.T)
+            dqkv_c = ops.qk_norm_rope3_bwd(dQ, dK, dV, qkv_c, w.wq_c, w.wk_c, None, None, B, Mt, H, S, N, gq_c, gk_c, m.T)
+        elif mod.kv_merge_attn:
             dQ, dK, dV = ops.attn_bwd(Q, K, V, Ox, Oc, dOx, dOc, lse, N, mod.scale, m.T, s_kv=S // 2)
             dqkv_x, dqkv_c = ops.qk_norm_rope_bwd_merge_pair(dQ, dK, dV, (qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], N, 0, gq_x, gk_x),
                                                              (qkv_c, w.wq_c, w.wk_c, None, None, Mt, N, gq_c, gk_c), B, H, S, m.T)
@@ -93,13 +104,17 @@ class Attention(nn.Module):
             raise RuntimeError(f"attn_type must be 'softmax' or 'softmax_flash' on the HIP path, but got {attn_type}")
         if not dual or causal or qk_half_dim or emb_dim is not None:
             raise RuntimeError("Attention: only the dual-stream, non-causal configuration of the trained model is implemented")
-        if positional_encoding != "RoPE2d":
-            raise RuntimeError("Attention: only positional_encoding='RoPE2d' is implemented")
+        if positional_encoding not in ("RoPE2d", "RoPE2dV2"):
+            raise RuntimeError("Attention: only positional_encoding='RoPE2d' and 'RoPE2dV2' are implemented")
         if dim % num_heads or dim // num_heads not in _lib.HEAD_DIMS:
             raise RuntimeError(f"Attention: head_dim = dim / num_heads must be 64 (the reference's dim = 64*num_heads convention, train.py:37-39) or 128, "
                                f"the widths the attention kernels are built for, but got dim={dim}, num_heads={num_heads}")
         if kv_merge_attn and dim // num_heads != 64:
             raise RuntimeError("Attention: kv_merge_attn is built for head_dim 64 only (the pair-averaging kernels mmdit_qk_norm_rope_*_merge / mmdit_attn_*_kv are 64 wide)")
+        if kv_merge_attn and positional_encoding == "RoPE2dV2":
+            raise RuntimeError("Attention: kv_merge_attn is not built for positional_encoding='RoPE2dV2' (the pair-averaging kernels "
+                               "mmdit_qk_norm_rope_*_merge rotate channel pairs; mmdit_qk_norm_rope3_* has no merging form)")
+        self.rope3 = positional_encoding == "RoPE2dV2"
         self.positional_encoding, self.kv_merge_attn, self.RoPE_Scale = positional_encoding, kv_merge_attn, RoPE_Scale
         self.layer_idx, self.dual, self.last = layer_idx, dual, last
         self.query_proj_x = nn.Linear(dim, dim, bias=False)
@@ -120,7 +135,10 @@ class Attention(nn.Module):
         self.k_norm_c = nn.RMSNorm(self.head_dim_qk)
         self.attn_type = attn_type   # both names run the same HIP flash kernel
         self.causal = causal
-        self.rotary_emb = RotaryEmbedding(self.head_dim_qk // 2, use_xpos=False, interpolate_factor=1 / RoPE_Scale)
+        if self.rope3:
+            self.rotary_emb = RoPE2D(self.head_dim_qk, interpolate_factor=1 / RoPE_Scale)
+        else:
+            self.rotary_emb = RotaryEmbedding(self.head_dim_qk // 2, use_xpos=False, interpolate_factor=1 / RoPE_Scale)
         self._pqkv_x = Pack([self.query_proj_x.weight, self.key_proj_x.weight, self.value_proj_x.weight])
         self._pqkv_c = Pack([self.query_proj_c.weight, self.key_proj_c.weight, self.value_proj_c.weight])
         self._po_x = Pack([self.out_proj_x.weight])
@@ -143,7 +161,7 @@ class Attention(nn.Module):
         return NS(Wqkv_x=self._pqkv_x.get(m), Wqkv_c=self._pqkv_c.get(m), Wo_x=self._po_x.get(m),
                   Wo_c=None if self.last else self._po_c.get(m),
                   wq_x=self.q_norm_x.weight.detach(), wk_x=self.k_norm_x.weight.detach(),
-                  wq_c=self.q_norm_c.weight.detach(), wk_c=self.k_norm_c.weight.detach(), kv_merge=bool(self.kv_merge_attn), hd=self.head_dim)
+                  wq_c=self.q_norm_c.weight.detach(), wk_c=self.k_norm_c.weight.detach(), kv_merge=bool(self.kv_merge_attn), hd=self.head_dim, rope3=self.rope3)
 
     def scatter_grads(self, g, out: dict):
         self._pqkv_x.split_grad(g.Wqkv_x, out)

@@ -1,5 +1,5 @@
 """PatchEmbed: mirror of the reference's src/blocks/ImagePositionalEncoding.py PatchEmbed
-(ctor 78-141, forward 175-187) for the trained configuration: pos_embed disabled (RoPE2d), no
+(ctor 78-141, forward 175-187) for the trained configuration: pos_embed disabled (RoPE2d, RoPE2dV2), no
 layer norm, flatten=True, bias=False.  The stride-p conv is executed as gather + MFMA GEMM."""
 import torch
 from torch import nn
@@ -37,7 +37,7 @@ class PatchEmbed(nn.Module):
         if layer_norm or bias or not flatten:
             raise RuntimeError("PatchEmbed: only layer_norm=False, bias=False, flatten=True (the reference's call, diff_model.py:193-205) is implemented")
         if pos_embed_type in ("absolute", "sincos"):
-            raise RuntimeError("PatchEmbed: absolute sin-cos position tables are not part of the trained configuration (RoPE2d)")
+            raise RuntimeError("PatchEmbed: absolute sin-cos position tables are not part of the trained configuration (RoPE2d / RoPE2dV2)")
         self.patch_size = patch_size
         self.flatten, self.layer_norm = flatten, layer_norm
         self.height, self.width = height // patch_size, width // patch_size

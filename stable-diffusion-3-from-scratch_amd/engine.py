@@ -330,6 +330,10 @@ def block_fwd(m, w, X, C, y, dims, rope, cond=None, keep=True, lazy=False):
     B, N, Mt, H, d = dims
     S, dev = N + Mt, (X.x if isinstance(X, Pending) else X).device
     both = not w.last
+    if w.rope3 and m.fp8:
+        raise RuntimeError("RoPE2dV2: no fp8 / mxfp8 path")      # (direct engine use; diff_model.set_precision refuses it first)
+    if w.rope3 and w.kv_merge:
+        raise RuntimeError("RoPE2dV2: kv_merge_attn is not built (no pair-averaging form of mmdit_qk_norm_rope3_fwd)")      # (direct engine use; Attention refuses it at construction)
     sv = NS(y=y)
     if cond is not None:
         sv.pre, sv.yp, sv.mod = cond
@@ -351,6 +355,9 @@ def block_fwd(m, w, X, C, y, dims, rope, cond=None, keep=True, lazy=False):
     # kv_merge_attn (Attention.py:243-251): the keys / values of adjacent token pairs are averaged -- K / V have S / 2 rows.  A GEMM epilogue sees
     # one token per row, so the plain grouped QKV GEMM and the merging norm / RoPE kernel run instead of the fused launch
     merge = w.kv_merge
+    # positional_encoding="RoPE2dV2": channel triples rotated by a row and a column angle (ops.qk_norm_rope3_*) -- the QKV epilogue and the fused
+    # attention backward rotate pairs, so the block takes the plain grouped QKV GEMM, the row kernel and ops.attn_fwd / attn_bwd
+    rope3 = w.rope3      # (its combinations with fp8 / mxfp8 and kv_merge_attn were refused on entry)
     if merge:
         assert N % 2 == 0 and Mt % 2 == 0, "Merge attention requires an even number of keys"
         if m.fp8:
@@ -361,7 +368,7 @@ def block_fwd(m, w, X, C, y, dims, rope, cond=None, keep=True, lazy=False):
     else:
         sv.K, sv.V = torch.empty_like(sv.Q), torch.empty_like(sv.Q)
     fused = None
-    if not merge and _QKV_FUSE and m.fast and dev.type == "cuda" and m.T == BF16 and (not m.fp8 or mxf) and hd == 64:
+    if not merge and not rope3 and _QKV_FUSE and m.fast and dev.type == "cuda" and m.T == BF16 and (not m.fp8 or mxf) and hd == 64:
         # QK-norm + RoPE + joint-layout store in the QKV GEMM's epilogue (one launch, no second pass over the raw projection); None: the
         # planner would not give these problems to a kernel with that epilogue (bf16: the lean wide-slot kernel; MX operands: the 8-phase kernel)
         qp = [dict(A=sv.ln1x, B=w.Wqkv_x, out_dtype=m.T, precision=m.prec), dict(A=sv.ln1c, B=w.Wqkv_c, out_dtype=m.T, precision=m.prec)]
@@ -377,6 +384,8 @@ def block_fwd(m, w, X, C, y, dims, rope, cond=None, keep=True, lazy=False):
         sv.qkv_x, sv.qkv_c = _group(m, [dict(A=sv.ln1x, B=w.Wqkv_x, out_dtype=m.T), dict(A=sv.ln1c, B=w.Wqkv_c, out_dtype=m.T)], fp8=True)
     if fused is not None:
         pass
+    elif rope3:
+        ops.qk_norm_rope3_fwd_pair((sv.qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], N, 0), (sv.qkv_c, w.wq_c, w.wk_c, None, None, Mt, N), B, H, S, sv.Q, sv.K, sv.V)
     elif merge:
         ops.qk_norm_rope_fwd_merge_pair((sv.qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], N, 0), (sv.qkv_c, w.wq_c, w.wk_c, None, None, Mt, N), B, H, S, sv.Q, sv.K, sv.V)
     elif _LN_PAIR and dev.type == "cuda":      # image + text rows in one launch
@@ -474,6 +483,9 @@ def _qk_bwd_two_pass(m, w, sv, g, dOx, dOc, dims, rope, dev):
         return ops.qk_norm_rope_bwd_merge_pair(dQ, dK, dV, (sv.qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], N, 0, g.wq_x, g.wk_x),
                                                (sv.qkv_c, w.wq_c, w.wk_c, None, None, Mt, N, g.wq_c, g.wk_c), B, H, S, m.T)
     dQ, dK, dV = ops.attn_bwd(sv.Q, sv.K, sv.V, sv.Ox, sv.Oc, dOx, dOc, sv.lse, N, w.hd ** -0.5, m.T)
+    if w.rope3:
+        return ops.qk_norm_rope3_bwd_pair(dQ, dK, dV, (sv.qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], N, 0, g.wq_x, g.wk_x),
+                                          (sv.qkv_c, w.wq_c, w.wk_c, None, None, Mt, N, g.wq_c, g.wk_c), B, H, S, m.T)
     if _LN_PAIR and dev.type == "cuda":
         return ops.qk_norm_rope_bwd_pair(dQ, dK, dV, (sv.qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], N, 0, g.wq_x, g.wk_x),
                                          (sv.qkv_c, w.wq_c, w.wk_c, None, None, Mt, N, g.wq_c, g.wk_c), B, H, S, m.T)
@@ -601,7 +613,7 @@ def block_bwd(m, w, sv, dX2, dC2, dy_acc, dims, rope, defer_cond=False, st=None,
     # ---- attention core + QK norm / RoPE
     # the QK-norm + RoPE backward runs in the epilogues of the attention backward kernels (ops.attn_bwd_qk) when the shapes allow it:
     # no dQ / dK / dV round trip, one pass less (MMDIT_ATTN_QK_FUSE=0: the two-pass form).  Head width 64 only (attn_bwd_qk_ok): the literals below are its
-    if not w.kv_merge and _QK_FUSE and m.fast and dev.type == "cuda" and ops.attn_bwd_qk_ok(sv.Q, N, sv.qkv_x) and g.wq_x.data_ptr() + 768 == g.wk_c.data_ptr():
+    if not w.kv_merge and not w.rope3 and _QK_FUSE and m.fast and dev.type == "cuda" and ops.attn_bwd_qk_ok(sv.Q, N, sv.qkv_x) and g.wq_x.data_ptr() + 768 == g.wk_c.data_ptr():
         dqkv_x, dqkv_c = ops.attn_bwd_qk(sv.Q, sv.K, sv.V, sv.Ox, sv.Oc, dOx, dOc, sv.lse, N, 64 ** -0.5, sv.qkv_x, sv.qkv_c, w.wq_x, w.wk_x, w.wq_c, w.wk_c,
                                          rope[0], rope[1], torch.as_strided(g.wq_x, (256,), (1,)))
     else:

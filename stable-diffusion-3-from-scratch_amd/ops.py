@@ -675,6 +675,72 @@ def qk_norm_rope_bwd_pair(dQ, dK, dV, img, txt, batch, heads, s_total, out_dtype
     return _qk("mmdit_qk_norm_rope_bwd", [img, txt], batch, heads, s_total, (dQ, dK, dV), out_dtype)
 
 
+def _qk_rope3(fn, streams, batch, heads, s_total, T3, out_dtype=None):
+    """One launch of a RoPE2dV2 entry point (include/mmdit_hip_rope3.h) over a list of 1 or 2 streams -- the tuples of _qk.  The head width is
+    taken from T3[0] = Q (forward) / dQ (backward); the row width, the norm-weight length and the table width (tokens, 2 * (hd // 3)) are
+    checked here, before the launch: the kernel indexes all of them by the head width."""
+    hd = _head_dim(T3[0], "QK-norm / RoPE2dV2")
+    bwd = out_dtype is not None
+    for t in T3:
+        if tuple(t.shape) != (batch, heads, s_total, hd) or t.dtype != T3[0].dtype or (not bwd and t.dtype != torch.bfloat16):
+            raise RuntimeError(f"{fn}: {'dQ / dK / dV' if bwd else 'Q / K / V (bfloat16)'} are (batch, heads, s_total, head_dim) = {(batch, heads, s_total, hd)} of one dtype, "
+                               f"got {t.dtype} {tuple(t.shape)}")
+        _c(t)
+    probs, outs = (_lib.QkProblem * len(streams))(), []
+    for q, st in zip(probs, streams):
+        qkv, wq, wk, rc, rs, tokens, tok0 = st[:7]
+        if qkv.dim() != 2 or tuple(qkv.shape) != (batch * tokens, 3 * heads * hd) or wq.numel() != hd or wk.numel() != hd:
+            raise RuntimeError(f"{fn}: qkv rows are (batch * tokens, 3 * heads * {hd}) = {(batch * tokens, 3 * heads * hd)}, norm weights {hd} wide; got {tuple(qkv.shape)}, "
+                               f"{wq.numel()}, {wk.numel()}")
+        if (rc is None) != (rs is None):
+            raise RuntimeError(f"{fn}: the cos and the sin table come together (or neither: the text stream)")
+        for tb in (rc, rs):
+            if tb is not None and (tuple(tb.shape) != (tokens, 2 * (hd // 3)) or tb.dtype != torch.float32):
+                raise RuntimeError(f"{fn}: the RoPE2dV2 tables are fp32 (tokens, 2 * (head_dim // 3)) = {(tokens, 2 * (hd // 3))}, got {tb.dtype} {tuple(tb.shape)}")
+            if tb is not None:
+                _c(tb)
+        if tokens < 1 or tok0 < 0 or tok0 + tokens > s_total:
+            raise RuntimeError(f"{fn}: tokens [{tok0}, {tok0 + tokens}) are outside the joint sequence of {s_total}")
+        if wq.dtype != torch.float32 or wk.dtype != torch.float32:
+            raise RuntimeError(f"{fn}: the norm weights are fp32")
+        q.qkv, q.wq, q.wk, q.rope_cos, q.rope_sin, q.tokens, q.tok0 = _p(_c(qkv)), _p(_c(wq)), _p(_c(wk)), _p(rc), _p(rs), tokens, tok0
+        if bwd:
+            if any(t.numel() != hd or t.dtype != torch.float32 for t in st[7:9]):
+                raise RuntimeError(f"{fn}: dwq / dwk are {hd} fp32 values")
+            dqkv = torch.empty(qkv.shape, dtype=out_dtype, device=qkv.device)
+            q.dqkv, q.dwq, q.dwk = _p(dqkv), _p(_c(st[7])), _p(_c(st[8]))
+            outs.append(dqkv)
+    if any(st[0].dtype != streams[0][0].dtype for st in streams):
+        raise RuntimeError(f"{fn}: the streams of one launch share the qkv dtype")
+    a, b, c = (_p(t) for t in T3)
+    launch, qkv_dt = getattr(_lib.lib(), fn), _dt(streams[0][0])
+    if not bwd:
+        check(launch(probs, len(streams), qkv_dt, batch, heads, hd, s_total, a, b, c, _s()), fn)
+    else:
+        check(launch(probs, len(streams), a, b, c, _dt(T3[0]), qkv_dt, _DT[out_dtype], batch, heads, hd, s_total, _s()), fn)
+    return outs
+
+
+def qk_norm_rope3_fwd(qkv, wq, wk, rope_cos, rope_sin, batch, tokens, heads, s_total, tok0, Q, K, V):
+    """positional_encoding="RoPE2dV2": per-head RMSNorm + rotation of channel triples + head split of one stream (mmdit_qk_norm_rope3_fwd);
+    rope_cos / rope_sin = rotary_embedding_2d_v2.RoPE2D.tables(), or None for the text stream (norm only, natural channel order)."""
+    _qk_rope3("mmdit_qk_norm_rope3_fwd", [(qkv, wq, wk, rope_cos, rope_sin, tokens, tok0)], batch, heads, s_total, (Q, K, V))
+
+
+def qk_norm_rope3_bwd(dQ, dK, dV, qkv, wq, wk, rope_cos, rope_sin, batch, tokens, heads, s_total, tok0, dwq, dwk, out_dtype):
+    return _qk_rope3("mmdit_qk_norm_rope3_bwd", [(qkv, wq, wk, rope_cos, rope_sin, tokens, tok0, dwq, dwk)], batch, heads, s_total, (dQ, dK, dV), out_dtype)[0]
+
+
+def qk_norm_rope3_fwd_pair(img, txt, batch, heads, s_total, Q, K, V):
+    """The image and the text rows of a RoPE2dV2 block in one launch; the argument tuples of qk_norm_rope_fwd_pair."""
+    _qk_rope3("mmdit_qk_norm_rope3_fwd", [img, txt], batch, heads, s_total, (Q, K, V))
+
+
+def qk_norm_rope3_bwd_pair(dQ, dK, dV, img, txt, batch, heads, s_total, out_dtype):
+    """Backward of both streams in one launch; the argument tuples of qk_norm_rope_bwd_pair.  Returns (dqkv_img, dqkv_txt), ADDS to dwq / dwk."""
+    return _qk_rope3("mmdit_qk_norm_rope3_bwd", [img, txt], batch, heads, s_total, (dQ, dK, dV), out_dtype)
+
+
 def _merge_status(status, what):
     if status == _lib.ERR_SHAPE:
         raise RuntimeError(f"{what}: kv_merge_attn averages adjacent token pairs -- the tokens of each stream, its offset and the joint length must be even")
