@@ -293,6 +293,10 @@ int mmdit_text_rmsnorm_bwd(const void* dout1, const void* dout2, int dout_dtype,
  * bwd: dqkv from dQ,dK,dV (dtype dq_dtype), dwq/dwk (64) accumulated atomically.
  * A LIST of count = 1 or 2 problems per launch (else MMDIT_ERR_ARG, nothing is launched): two are the image and the text rows of a block, which
  * write / read the same joint Q, K, V at their own token offset -- the arithmetic of two launches of one, one ramp-up and tail.
+ * A NULL operand, only one of the two tables, s_total <= 0, heads > 42 (a row is one workgroup of 24 * heads <= 1024 threads) or a token range outside
+ * [0, s_total]: MMDIT_ERR_ARG; batch * tokens > INT_MAX: MMDIT_ERR_SHAPE; another dtype (combination): MMDIT_ERR_DTYPE.  These four entry points and
+ * their namesakes at head width 128 and for RoPE2dV2 (declared in headers of their own) share one validator: the token range is summed in 64 bits and the row count is
+ * checked, which refuses only lists whose tok0 + tokens or batch * tokens overflowed int before (and were then accepted or refused by accident).
  * ------------------------------------------------------------------------- */
 typedef struct mmdit_qk_problem {
   const void* qkv; const float* wq; const float* wk; const float* rope_cos; const float* rope_sin; int tokens, tok0;
@@ -308,7 +312,8 @@ int mmdit_qk_norm_rope_bwd(const mmdit_qk_problem* probs, int count, const void*
  * mmdit_qk_norm_rope_fwd, bit for bit; K and V are (batch, heads, s_total / 2, 64), pair j of a stream at row tok0 / 2 + j.
  * bwd: dQ (batch, heads, s_total, 64), dK / dV (batch, heads, s_total / 2, 64): every token of a pair receives half of its merged row's
  * gradient, pushed through that token's own RoPE / norm backward; dqkv rows and the accumulated dwq / dwk as in mmdit_qk_norm_rope_bwd.
- * An odd tokens, tok0 or s_total: MMDIT_ERR_SHAPE, nothing is launched.  heads <= 21 (one pair per workgroup of 24 * heads <= 512 threads). */
+ * An odd tokens, tok0 or s_total: MMDIT_ERR_SHAPE, nothing is launched.  heads <= 21 (one pair per workgroup of 24 * heads <= 512 threads; more:
+ * MMDIT_ERR_ARG); the other checks as above. */
 int mmdit_qk_norm_rope_fwd_merge(const mmdit_qk_problem* probs, int count, int qkv_dtype, int batch, int heads, int s_total,
                                  void* Q, void* K, void* V, mmdit_stream_t stream);
 int mmdit_qk_norm_rope_bwd_merge(const mmdit_qk_problem* probs, int count, const void* dQ, const void* dK, const void* dV, int dq_dtype,

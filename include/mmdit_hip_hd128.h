@@ -22,7 +22,8 @@ extern "C" {
 #define MMDIT_ATTN_HD128_KEY_TILE 32
 #define MMDIT_ATTN_HD128_QUERY_TILE 128
 /* QK-norm / RoPE: a qkv row is one workgroup of 48 * heads threads, so heads <= 21; the backward packs 1024 / (48 * heads) rows into a
- * workgroup once every problem of the list has this many rows. */
+ * workgroup once every problem of the list has this many rows (the launch policy of the 64-wide entry points, whose row has 24 * heads threads:
+ * the two widths are one kernel source and one policy). */
 #define MMDIT_QK_HD128_MAX_HEADS 21
 #define MMDIT_QK_HD128_RL_MIN_ROWS 2048
 
@@ -51,7 +52,7 @@ int mmdit_attn_bwd_hd128(const void* Q, const void* K, const void* V, const void
  * qkv: (batch * tokens, 3 * heads * 128) rows of one stream = [q | k | v]; wq / wk: fp32 (128); rope_cos / rope_sin: fp32 (tokens, 128)
  * tables or NULL; writes bf16 Q, K, V (batch, heads, s_total, 128) at token offset tok0.  A list of count = 1 or 2 problems in one launch.
  * heads > MMDIT_QK_HD128_MAX_HEADS: MMDIT_ERR_SHAPE; qkv_dtype other than MMDIT_BF16 / MMDIT_F32: MMDIT_ERR_DTYPE; a NULL operand, a bad
- * count or a token range outside [0, s_total]: MMDIT_ERR_ARG. */
+ * count, s_total <= 0 or a token range outside [0, s_total]: MMDIT_ERR_ARG; batch * tokens > INT_MAX: MMDIT_ERR_SHAPE. */
 int mmdit_qk_norm_rope_fwd_hd128(const mmdit_qk_problem* probs, int count, int qkv_dtype, int batch, int heads, int s_total,
                                  void* Q, void* K, void* V, mmdit_stream_t stream);
 

@@ -2,13 +2,12 @@
 // All loads/stores are 8-16 B per lane; reductions over a row live in one 64-lane wave;
 // per-batch / per-column gradient sums are accumulated in registers over a row chunk and
 // flushed with fp32 atomics (caller zero-initialises the destination).
-#include "common.h"
-#include <float.h>
+#include "qk_rows.h"
+#include "../../include/mmdit_hip_hd128.h"
 
 namespace {
 
 constexpr float LN_EPS = 1e-5f;           // nn.LayerNorm default (Norm.py:10)
-constexpr float RMS_EPS = FLT_EPSILON;    // nn.RMSNorm(eps=None) on fp32 input
 
 // -------------------------------------------------------------------------------------------
 // adaLN forward: one wave per row, the row is kept in registers (NIT float4 per lane).
@@ -379,25 +378,22 @@ __global__ __launch_bounds__(512) void text_rms_bwd_kernel(TextRmsBwdHalf h0, Te
 }
 
 // -------------------------------------------------------------------------------------------
-// per-head QK RMSNorm + RoPE2d + head split.  8 lanes own one 64-wide head vector (8 elements each).
+// per-head QK RMSNorm + RoPE2d + head split at head width HD = 64 or 128.  CH = HD / 8 lanes own one head vector (8 elements each).
 // flat index over [row][part q/k/v][head][chunk] == memory order of a qkv row.
 // -------------------------------------------------------------------------------------------
-__device__ __forceinline__ float group8_sum(float v) {
-  v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64);
-  return v;
-}
 
-// Forward: same thread mapping as the backward kernel below -- a workgroup of 24 * heads threads is one qkv row (thread = (part,
+// Forward: same thread mapping as the backward kernel below -- a workgroup of 3 * CH * heads threads is one qkv row (thread = (part,
 // head, 8-element chunk), no per-element index divisions, norm weights in registers), rows blockIdx.x, + gridDim.x, ... two in
 // flight; with the grid a multiple of the tokens per sample all rows of a workgroup are the same token and the RoPE factors are
 // loaded once.
 // (bid, rstride) = this workgroup's index and the number of workgroups of ITS problem (the kernel runs a list of problems in one grid)
-template <typename TI>
+template <int HD, typename TI>
 __device__ __forceinline__ void qk_norm_rope_fwd_body(int bid, int rstride, const TI* __restrict__ qkv, const float* __restrict__ wq, const float* __restrict__ wk,
                                                       const float* __restrict__ rcos, const float* __restrict__ rsin,
                                                       int rows, int tokens, int heads, int s_total, int tok0,
                                                       bf16_t* __restrict__ Q, bf16_t* __restrict__ K, bf16_t* __restrict__ V) {
-  const int hc = threadIdx.x % (8 * heads), part = threadIdx.x / (8 * heads), head = hc >> 3, chunk = hc & 7;
+  constexpr int CH = HD / 8, LOG_CH = CH == 8 ? 3 : 4;
+  const int hc = threadIdx.x % (CH * heads), part = threadIdx.x / (CH * heads), head = hc >> LOG_CH, chunk = hc & (CH - 1);
   bf16_t* obase = part == 0 ? Q : part == 1 ? K : V;
   float w[8];
 #pragma unroll
@@ -407,8 +403,8 @@ __device__ __forceinline__ void qk_norm_rope_fwd_body(int bid, int rstride, cons
   float cs[2][8], sn[2][8];
   if (same_token && part < 2) {
     const int n = bid % tokens;
-    ld8(rcos + (int64_t)n * 64 + chunk * 8, cs[0]);
-    ld8(rsin + (int64_t)n * 64 + chunk * 8, sn[0]);
+    ld8(rcos + (int64_t)n * HD + chunk * 8, cs[0]);
+    ld8(rsin + (int64_t)n * HD + chunk * 8, sn[0]);
 #pragma unroll
     for (int e = 0; e < 8; e++) { cs[1][e] = cs[0][e]; sn[1][e] = sn[0][e]; }
   }
@@ -419,14 +415,14 @@ __device__ __forceinline__ void qk_norm_rope_fwd_body(int bid, int rstride, cons
 #pragma unroll
     for (int k = 0; k < 2; k++) {
       const int row = min(row0 + k * rstride, rows - 1);
-      ld8(qkv + (((int64_t)row * 3 + part) * heads + head) * 64 + chunk * 8, x[k]);
+      ld8(qkv + (((int64_t)row * 3 + part) * heads + head) * HD + chunk * 8, x[k]);
     }
     if (part < 2 && rcos && !same_token) {
 #pragma unroll
       for (int k = 0; k < 2; k++) {
         const int n = min(row0 + k * rstride, rows - 1) % tokens;
-        ld8(rcos + (int64_t)n * 64 + chunk * 8, cs[k]);
-        ld8(rsin + (int64_t)n * 64 + chunk * 8, sn[k]);
+        ld8(rcos + (int64_t)n * HD + chunk * 8, cs[k]);
+        ld8(rsin + (int64_t)n * HD + chunk * 8, sn[k]);
       }
     }
 #pragma unroll
@@ -438,7 +434,7 @@ __device__ __forceinline__ void qk_norm_rope_fwd_body(int bid, int rstride, cons
         float ss = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; e++) ss += x[k][e] * x[k][e];
-        const float rinv = rsqrtf(group8_sum(ss) * (1.f / 64.f) + RMS_EPS);
+        const float rinv = rsqrtf(group_sum<CH>(ss) * (1.f / HD) + RMS_EPS);
 #pragma unroll
         for (int e = 0; e < 8; e++) x[k][e] = x[k][e] * rinv * w[e];
         if (rcos) {
@@ -450,55 +446,59 @@ __device__ __forceinline__ void qk_norm_rope_fwd_body(int bid, int rstride, cons
           }
         }
       }
-      st8(obase + (((int64_t)b * heads + head) * s_total + tok0 + n) * 64 + chunk * 8, x[k]);
+      st8(obase + (((int64_t)b * heads + head) * s_total + tok0 + n) * HD + chunk * 8, x[k]);
     }
   }
 }
-// a list of one or two problems (workgroups [0, g0) = problem 0): the image and the text rows of a block write the same Q / K / V, different token ranges
-struct QkProb {
-  const void* qkv; const float* wq; const float* wk; const float* rcos; const float* rsin; int rows, tokens, tok0;
-  const void* dQ; const void* dK; const void* dV; void* dqkv; float* dwq; float* dwk;      // (backward only)
-};
-template <typename TI>
+template <int HD, typename TI>
 __global__ __launch_bounds__(1024) void qk_norm_rope_fwd_kernel(QkProb p0, QkProb p1, int g0, int heads, int s_total,
                                                                 bf16_t* __restrict__ Q, bf16_t* __restrict__ K, bf16_t* __restrict__ V) {
-  const bool first = (int)blockIdx.x < g0;     // (workgroup-uniform)
-  const QkProb& p = first ? p0 : p1;
-  qk_norm_rope_fwd_body<TI>(first ? (int)blockIdx.x : (int)blockIdx.x - g0, first ? g0 : (int)gridDim.x - g0, (const TI*)p.qkv, p.wq, p.wk, p.rcos, p.rsin,
-                            p.rows, p.tokens, heads, s_total, p.tok0, Q, K, V);
+  QK_SELECT(p, bid, nwg);
+  qk_norm_rope_fwd_body<HD, TI>(bid, nwg, (const TI*)p.qkv, p.wq, p.wk, p.rcos, p.rsin, p.rows, p.tokens, heads, s_total, p.tok0, Q, K, V);
 }
 
-// Backward: a workgroup has 24 * heads threads = one qkv row (thread = (part, head, 8-element chunk): no per-element index
+// How the backward holds the RoPE factors.  Width 64 runs QK_ONCE when every problem of the launch either has no RoPE or walks ONE token per
+// row lane (lanes % tokens == 0) and QK_PER_PAIR otherwise: the single copy is 16 registers fewer than the two, which keep the kernel at the
+// 128-VGPR cap of a 1024-thread workgroup with spills.  Width 128 runs QK_PER_ROW only (no width has been measured in another mode).
+enum QkFactors {
+  QK_ONCE,          // one copy, loaded once
+  QK_PER_PAIR,      // two copies, loaded with each pair of rows before their use (once when the lane sits on one token: tested at run time)
+  QK_PER_ROW,       // one copy, reloaded per row right before its use (loaded once when the lane sits on one token: tested at run time)
+};
+
+// Backward: a workgroup has 3 * CH * heads threads = one qkv row (thread = (part, head, 8-element chunk): no per-element index
 // divisions, the q/k norm weights stay in registers) and walks rows blockIdx.x, + gridDim.x, ... two at a time; the grid is
-// small (2 workgroups per CU) because every workgroup ends with 128 global atomics on the same two cache lines.
-// FAST: every problem of the launch either has no RoPE or walks ONE token per row lane (lanes % tokens == 0): a single copy of the RoPE
-// factors, loaded once -- 16 registers fewer than the general path, which kept the kernel at the 128-VGPR cap with spills
-template <bool FAST, typename TG, typename TI, typename TO>
+// small (2 workgroups per CU) because every workgroup ends with 2 * HD global atomics on the same cache lines.
+template <int HD, QkFactors F, typename TG, typename TI, typename TO>
 __device__ __forceinline__ void qk_norm_rope_bwd_body(int bid, int rstride, const TG* __restrict__ dQ, const TG* __restrict__ dK, const TG* __restrict__ dV,
                                                       const TI* __restrict__ qkv, const float* __restrict__ wq, const float* __restrict__ wk,
                                                       const float* __restrict__ rcos, const float* __restrict__ rsin,
                                                       int rows, int tokens, int heads, int s_total, int tok0,
                                                       TO* __restrict__ dqkv, float* __restrict__ dwq, float* __restrict__ dwk) {
-  __shared__ float sdw[2][64];
-  for (int i = threadIdx.x; i < 128; i += blockDim.x) sdw[i >> 6][i & 63] = 0.f;
+  constexpr int CH = HD / 8, LOG_CH = CH == 8 ? 3 : 4, LOG_HD = LOG_CH + 3;
+  __shared__ float sdw[2][HD];
+  for (int i = threadIdx.x; i < 2 * HD; i += blockDim.x) sdw[i >> LOG_HD][i & (HD - 1)] = 0.f;
   __syncthreads();
-  // a workgroup is RL row lanes of 24 * heads threads: RL rows per iteration share ONE set of 128 global atomics at the end
-  const int per_row = 24 * heads, rlane = threadIdx.x / per_row, t = threadIdx.x - rlane * per_row;
+  // a workgroup is RL row lanes of 3 * CH * heads threads: RL rows per iteration share ONE set of 2 * HD global atomics at the end
+  const int per_row = 3 * CH * heads, rlane = threadIdx.x / per_row, t = threadIdx.x - rlane * per_row;
   { const int RL = blockDim.x / per_row; bid = bid * RL + rlane; rstride *= RL; }
-  const int hc = t % (8 * heads), part = t / (8 * heads), head = hc >> 3, chunk = hc & 7;
+  const int hc = t % (CH * heads), part = t / (CH * heads);
+  // (width 128 keeps the signed division of the source it had: the same values as the shift and mask, hc >= 0, in six more instructions)
+  const int head = HD == 64 ? hc >> LOG_CH : hc / CH, chunk = HD == 64 ? hc & (CH - 1) : hc % CH;
   const TG* gbase = part == 0 ? dQ : part == 1 ? dK : dV;
   float w[8], aw[8];
 #pragma unroll
   for (int e = 0; e < 8; e++) { w[e] = 0.f; aw[e] = 0.f; }
   if (part < 2) ld8((part == 0 ? wq : wk) + chunk * 8, w);
-  // grid a multiple of the tokens per sample: every row of this workgroup is the same token, its RoPE factors are loaded once
-  const bool same_token = FAST ? rcos != nullptr : (rcos && rstride % tokens == 0);
-  float cs[FAST ? 1 : 2][8], sn[FAST ? 1 : 2][8];
+  // grid a multiple of the tokens per sample: every row of this lane is the same token, its RoPE factors are loaded once
+  const bool same_token = F == QK_ONCE ? rcos != nullptr : (rcos && rstride % tokens == 0);
+  constexpr int NF = F == QK_PER_PAIR ? 2 : 1;
+  float cs[NF][8], sn[NF][8];
   if (same_token && part < 2) {
     const int n = bid % tokens;
-    ld8(rcos + (int64_t)n * 64 + chunk * 8, cs[0]);
-    ld8(rsin + (int64_t)n * 64 + chunk * 8, sn[0]);
-    if constexpr (!FAST) {
+    ld8(rcos + (int64_t)n * HD + chunk * 8, cs[0]);
+    ld8(rsin + (int64_t)n * HD + chunk * 8, sn[0]);
+    if constexpr (F == QK_PER_PAIR) {
 #pragma unroll
       for (int e = 0; e < 8; e++) { cs[1][e] = cs[0][e]; sn[1][e] = sn[0][e]; }
     }
@@ -511,18 +511,18 @@ __device__ __forceinline__ void qk_norm_rope_bwd_body(int bid, int rstride, cons
     for (int k = 0; k < 2; k++) {
       const int row = min(row0 + k * rstride, rows - 1);
       const int n = row % tokens, b = row / tokens;
-      ld8_nt(gbase + (((int64_t)b * heads + head) * s_total + tok0 + n) * 64 + chunk * 8, dz[k]);      // (single use; the saved qkv below: last use)
+      ld8_nt(gbase + (((int64_t)b * heads + head) * s_total + tok0 + n) * HD + chunk * 8, dz[k]);      // (single use; the saved qkv below: last use)
     }
     if (part < 2) {
 #pragma unroll
       for (int k = 0; k < 2; k++) {
         const int row = min(row0 + k * rstride, rows - 1);
-        ld8_nt(qkv + (((int64_t)row * 3 + part) * heads + head) * 64 + chunk * 8, x[k]);
-        if constexpr (!FAST) {
+        ld8_nt(qkv + (((int64_t)row * 3 + part) * heads + head) * HD + chunk * 8, x[k]);
+        if constexpr (F == QK_PER_PAIR) {
           if (rcos && !same_token) {
             const int n = row % tokens;
-            ld8(rcos + (int64_t)n * 64 + chunk * 8, cs[k]);
-            ld8(rsin + (int64_t)n * 64 + chunk * 8, sn[k]);
+            ld8(rcos + (int64_t)n * HD + chunk * 8, cs[k]);
+            ld8(rsin + (int64_t)n * HD + chunk * 8, sn[k]);
           }
         }
       }
@@ -535,13 +535,20 @@ __device__ __forceinline__ void qk_norm_rope_bwd_body(int bid, int rstride, cons
         float ss = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; e++) ss += x[k][e] * x[k][e];
-        const float rinv = rsqrtf(group8_sum(ss) * (1.f / 64.f) + RMS_EPS);
+        const float rinv = rsqrtf(group_sum<CH>(ss) * (1.f / HD) + RMS_EPS);
         if (rcos) {
+          const int f = F == QK_PER_PAIR ? k : 0;
+          if constexpr (F == QK_PER_ROW) {
+            if (!same_token) {
+              ld8(rcos + (int64_t)(row % tokens) * HD + chunk * 8, cs[0]);
+              ld8(rsin + (int64_t)(row % tokens) * HD + chunk * 8, sn[0]);
+            }
+          }
 #pragma unroll
           for (int p = 0; p < 4; p++) {
             float da = dz[k][2 * p], db = dz[k][2 * p + 1];
-            dz[k][2 * p] = da * cs[FAST ? 0 : k][2 * p] + db * sn[FAST ? 0 : k][2 * p + 1];
-            dz[k][2 * p + 1] = db * cs[FAST ? 0 : k][2 * p + 1] - da * sn[FAST ? 0 : k][2 * p];
+            dz[k][2 * p] = da * cs[f][2 * p] + db * sn[f][2 * p + 1];
+            dz[k][2 * p + 1] = db * cs[f][2 * p + 1] - da * sn[f][2 * p];
           }
         }
         float dot = 0.f;
@@ -553,27 +560,26 @@ __device__ __forceinline__ void qk_norm_rope_bwd_body(int bid, int rstride, cons
           dot += dz[k][e] * xh;
           x[k][e] = xh;
         }
-        dot = group8_sum(dot) * (1.f / 64.f);
+        dot = group_sum<CH>(dot) * (1.f / HD);
 #pragma unroll
         for (int e = 0; e < 8; e++) dz[k][e] = rinv * (dz[k][e] - x[k][e] * dot);
       }
-      st8(dqkv + (((int64_t)row * 3 + part) * heads + head) * 64 + chunk * 8, dz[k]);
+      st8(dqkv + (((int64_t)row * 3 + part) * heads + head) * HD + chunk * 8, dz[k]);
     }
   }
-  // weight gradients: sum over rows (done) and heads: LDS atomics per (part, column), then 128 global atomics per workgroup
+  // weight gradients: sum over rows (done) and heads: LDS atomics per (part, column), then 2 * HD global atomics per workgroup
   if (part < 2) {
 #pragma unroll
     for (int e = 0; e < 8; e++) atomicAdd(&sdw[part][chunk * 8 + e], aw[e]);
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < 128; i += blockDim.x) atomicAdd((i < 64 ? dwq : dwk) + (i & 63), sdw[i >> 6][i & 63]);
+  for (int i = threadIdx.x; i < 2 * HD; i += blockDim.x) atomicAdd((i < HD ? dwq : dwk) + (i & (HD - 1)), sdw[i >> LOG_HD][i & (HD - 1)]);
 }
-template <bool FAST, typename TG, typename TI, typename TO>
+template <int HD, QkFactors F, typename TG, typename TI, typename TO>
 __global__ __launch_bounds__(1024) void qk_norm_rope_bwd_kernel(QkProb p0, QkProb p1, int g0, int heads, int s_total) {
-  const bool first = (int)blockIdx.x < g0;     // (workgroup-uniform)
-  const QkProb& p = first ? p0 : p1;
-  qk_norm_rope_bwd_body<FAST, TG, TI, TO>(first ? (int)blockIdx.x : (int)blockIdx.x - g0, first ? g0 : (int)gridDim.x - g0, (const TG*)p.dQ, (const TG*)p.dK, (const TG*)p.dV,
-                                    (const TI*)p.qkv, p.wq, p.wk, p.rcos, p.rsin, p.rows, p.tokens, heads, s_total, p.tok0, (TO*)p.dqkv, p.dwq, p.dwk);
+  QK_SELECT(p, bid, nwg);
+  qk_norm_rope_bwd_body<HD, F, TG, TI, TO>(bid, nwg, (const TG*)p.dQ, (const TG*)p.dK, (const TG*)p.dV, (const TI*)p.qkv, p.wq, p.wk, p.rcos, p.rsin,
+                                           p.rows, p.tokens, heads, s_total, p.tok0, (TO*)p.dqkv, p.dwq, p.dwk);
 }
 
 // -------------------------------------------------------------------------------------------
@@ -614,7 +620,7 @@ __device__ __forceinline__ void qk_merge_fwd_body(int bid, int pstride, const TI
         float ss = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; e++) ss += x[k][e] * x[k][e];
-        const float rinv = rsqrtf(group8_sum(ss) * (1.f / 64.f) + RMS_EPS);
+        const float rinv = rsqrtf(group_sum<8>(ss) * (1.f / 64.f) + RMS_EPS);
 #pragma unroll
         for (int e = 0; e < 8; e++) x[k][e] = x[k][e] * rinv * w[e];
         if (rcos) {
@@ -641,10 +647,8 @@ __device__ __forceinline__ void qk_merge_fwd_body(int bid, int pstride, const TI
 template <typename TI>
 __global__ __launch_bounds__(512) void qk_merge_fwd_kernel(QkProb p0, QkProb p1, int g0, int heads, int s_total,
                                                             bf16_t* __restrict__ Q, bf16_t* __restrict__ K, bf16_t* __restrict__ V) {
-  const bool first = (int)blockIdx.x < g0;     // (workgroup-uniform)
-  const QkProb& p = first ? p0 : p1;
-  qk_merge_fwd_body<TI>(first ? (int)blockIdx.x : (int)blockIdx.x - g0, first ? g0 : (int)gridDim.x - g0, (const TI*)p.qkv, p.wq, p.wk, p.rcos, p.rsin,
-                        p.rows >> 1, p.tokens, heads, s_total, p.tok0, Q, K, V);
+  QK_SELECT(p, bid, nwg);
+  qk_merge_fwd_body<TI>(bid, nwg, (const TI*)p.qkv, p.wq, p.wk, p.rcos, p.rsin, p.rows >> 1, p.tokens, heads, s_total, p.tok0, Q, K, V);
 }
 
 template <typename TG, typename TI, typename TO>
@@ -687,7 +691,7 @@ __device__ __forceinline__ void qk_merge_bwd_body(int bid, int pstride, const TG
         float ss = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; e++) ss += x[k][e] * x[k][e];
-        const float rinv = rsqrtf(group8_sum(ss) * (1.f / 64.f) + RMS_EPS);
+        const float rinv = rsqrtf(group_sum<8>(ss) * (1.f / 64.f) + RMS_EPS);
         if (rcos) {      // transpose of the rotation
 #pragma unroll
           for (int p = 0; p < 4; p++) {
@@ -705,7 +709,7 @@ __device__ __forceinline__ void qk_merge_bwd_body(int bid, int pstride, const TG
           dot += dz[k][e] * xh;
           x[k][e] = xh;
         }
-        dot = group8_sum(dot) * (1.f / 64.f);
+        dot = group_sum<8>(dot) * (1.f / 64.f);
 #pragma unroll
         for (int e = 0; e < 8; e++) dz[k][e] = rinv * (dz[k][e] - x[k][e] * dot);
       }
@@ -722,9 +726,8 @@ __device__ __forceinline__ void qk_merge_bwd_body(int bid, int pstride, const TG
 }
 template <typename TG, typename TI, typename TO>
 __global__ __launch_bounds__(512) void qk_merge_bwd_kernel(QkProb p0, QkProb p1, int g0, int heads, int s_total) {
-  const bool first = (int)blockIdx.x < g0;     // (workgroup-uniform)
-  const QkProb& p = first ? p0 : p1;
-  qk_merge_bwd_body<TG, TI, TO>(first ? (int)blockIdx.x : (int)blockIdx.x - g0, first ? g0 : (int)gridDim.x - g0, (const TG*)p.dQ, (const TG*)p.dK, (const TG*)p.dV,
+  QK_SELECT(p, bid, nwg);
+  qk_merge_bwd_body<TG, TI, TO>(bid, nwg, (const TG*)p.dQ, (const TG*)p.dK, (const TG*)p.dV,
                                 (const TI*)p.qkv, p.wq, p.wk, p.rcos, p.rsin, p.rows >> 1, p.tokens, heads, s_total, p.tok0, (TO*)p.dqkv, p.dwq, p.dwk);
 }
 
@@ -1240,112 +1243,105 @@ extern "C" int mmdit_text_rmsnorm_bwd(const void* dout1, const void* dout2, int 
   return mmdit_launch_status();
 }
 
-// Launch shape of the QK-norm/RoPE backward: RL row lanes per workgroup (as many as fit 1024 threads; every workgroup ends with 128
-// global atomics on the same two cache lines, so fewer, fatter workgroups), `lanes` rows in flight per iteration pair, a multiple of the
-// tokens per sample when RoPE applies (same token for all rows of a lane: factors loaded once).
-static int qk_bwd_rl(int heads, int min_rows) {      // (restated in tests/test_rowops_edges_gpu.py)
+// Launch shape of the QK-norm/RoPE kernels at either width: `lanes` rows in flight per iteration pair, RL row lanes per workgroup; with RoPE
+// a multiple of the tokens per sample when one fits (same token for all rows of a lane: factors loaded once).
+// Backward: as many row lanes as fit 1024 threads once every problem of the list has QK_RL_MIN_ROWS rows (every workgroup ends with 2 * HD
+// global atomics on the same cache lines, so fewer, fatter workgroups), 768 lanes then, 512 workgroups of one row below.  Forward: 1024 rows.
+constexpr int QK_RL_MIN_ROWS = 2048;
+static_assert(QK_RL_MIN_ROWS == MMDIT_QK_HD128_RL_MIN_ROWS && 1024 / (3 * 128 / 8) == MMDIT_QK_HD128_MAX_HEADS, "include/mmdit_hip_hd128.h documents this policy");
+static int qk_rl(int row_threads, int min_rows) {      // (restated at width 64 in tests/test_rowops_edges_gpu.py)
   static const int env = [] { const char* e = mmdit_exp_env("MMDIT_QK_RL"); return e ? atoi(e) : 0; }();
-  int rl = 1024 / (24 * heads);
+  int rl = 1024 / row_threads;
   if (env > 0 && env < rl) rl = env;
-  if (rl < 1 || min_rows < 2048) rl = 1;
+  if (rl < 1 || min_rows < QK_RL_MIN_ROWS) rl = 1;
   return rl;
 }
-static int qk_bwd_grid(int rows, int tokens, bool rope, int& rl) {      // (restated in tests/test_rowops_edges_gpu.py)
-  static const int lanes_max = [] { const char* e = mmdit_exp_env("MMDIT_QK_LANES"); return e ? atoi(e) : 768; }();
-  if (rl == 1) {
-    int g = rows < 512 ? rows : 512;
-    if (rope && tokens <= 1024 && rows >= tokens) g = (g / tokens > 0 ? g / tokens : 1) * tokens;
-    return g;
+static int qk_bwd_lanes(int rl) {
+  static const int env = [] { const char* e = mmdit_exp_env("MMDIT_QK_LANES"); return e ? atoi(e) : 768; }();
+  return rl > 1 ? env : 512;
+}
+static int qk_grid(int hd, int rows, int tokens, bool rope, int lanes_max, int rl) {      // (restated at width 64 in tests/test_rowops_edges_gpu.py)
+  const int lanes = rows < lanes_max ? rows : lanes_max;
+  if (rope && tokens <= lanes) {
+    int k = lanes / tokens;
+    while (k > 1 && (k * tokens) % rl) k--;
+    if ((k * tokens) % rl == 0) return k * tokens / rl;
   }
-  if (!rope) return lanes_max / rl;
-  if (tokens > lanes_max) return tokens <= 2048 && tokens % rl == 0 ? tokens / rl : lanes_max / rl;      // (one lane per token: 512^2 images, 1024 tokens)
-  int k = lanes_max / tokens;
-  while (k > 1 && (k * tokens) % rl) k--;
-  if ((k * tokens) % rl) return lanes_max / rl;       // (lanes then walk all tokens: factors reloaded per row)
-  return k * tokens / rl;
+  // one lane per token (512^2 images: 1024 tokens) when the tokens of a sample exceed the lanes -- width 64 only: unmeasured at 128
+  if (hd == 64 && rope && tokens > lanes && tokens <= rows && tokens <= (rl > 1 ? 2048 : 1024) && tokens % rl == 0) return tokens / rl;
+  return lanes / rl > 0 ? lanes / rl : 1;       // (with RoPE the lanes then walk all tokens: factors reloaded per row)
 }
 
-// pointers and token range of one QK-norm + RoPE problem (bwd: its gradient pointers too)
-static int qk_check(const mmdit_qk_problem* p, int s_total, bool bwd) {
-  if (!(p->qkv && p->wq && p->wk && p->tokens > 0 && p->tok0 >= 0 && p->tok0 + p->tokens <= s_total && (p->rope_cos == nullptr) == (p->rope_sin == nullptr))) return MMDIT_ERR_ARG;
-  if (bwd && !(p->dqkv && p->dwq && p->dwk)) return MMDIT_ERR_ARG;
-  return 0;
-}
-// kv_merge_attn averages adjacent token pairs, and a pair never straddles two streams or two samples: an odd tokens, tok0 or s_total is MMDIT_ERR_SHAPE
-static int qk_merge_check(const mmdit_qk_problem* p, int s_total, bool bwd) {
-  if (int e = qk_check(p, s_total, bwd)) return e;
-  if ((p->tokens | p->tok0 | s_total) & 1) return MMDIT_ERR_SHAPE;
-  return 0;
-}
-// The four QK-norm + RoPE launchers (plain and kv_merge, forward and backward) validate their list here, once, and get the kernel-side problems
-// back.  max_threads: 1024, or 512 for the merge kernels (255 VGPRs: both rows of a pair and their factors stay in registers) -- a workgroup
-// is one row (one pair) of 24 * heads threads.  bwd: dQ / dK / dV and the per-problem gradient pointers are required.  merge: qk_merge_check.
-static int qk_list(const mmdit_qk_problem* probs, int count, int batch, int heads, int s_total, int max_threads, bool merge,
-                   bool bwd, const void* dQ, const void* dK, const void* dV, QkProb (&q)[2]) {
-  MMDIT_CHECK_ARG(probs && count >= 1 && count <= 2 && batch > 0 && heads > 0 && 24 * heads <= max_threads && (!bwd || (dQ && dK && dV)));
-  for (int i = 0; i < count; i++) {
-    const mmdit_qk_problem* p = probs + i;
-    if (int e = merge ? qk_merge_check(p, s_total, bwd) : qk_check(p, s_total, bwd)) return e;
-    q[i] = QkProb{p->qkv, p->wq, p->wk, p->rope_cos, p->rope_sin, batch * p->tokens, p->tokens, p->tok0, dQ, dK, dV,
-                  bwd ? p->dqkv : nullptr, bwd ? p->dwq : nullptr, bwd ? p->dwk : nullptr};
-  }
-  return 0;
-}
-// dtype combinations of the backward kernels (dQ / dK / dV, saved qkv, dqkv): 0 all bf16, 1 all fp32, 2 bf16 gradients of an fp32 projection
-static int qk_bwd_combo(int dq_dtype, int qkv_dtype, int dqkv_dtype) {
-  return (dq_dtype == MMDIT_BF16 && qkv_dtype == MMDIT_BF16 && dqkv_dtype == MMDIT_BF16) ? 0
-       : (dq_dtype == MMDIT_F32 && qkv_dtype == MMDIT_F32 && dqkv_dtype == MMDIT_F32)    ? 1
-       : (dq_dtype == MMDIT_BF16 && qkv_dtype == MMDIT_F32 && dqkv_dtype == MMDIT_F32)   ? 2 : -1;
-}
-
-extern "C" int mmdit_qk_norm_rope_fwd(const mmdit_qk_problem* probs, int count, int qkv_dtype, int batch, int heads, int s_total,
-                                      void* Q, void* K, void* V, mmdit_stream_t stream) {
+template <int HD>
+static int qk_fwd_launch(const mmdit_qk_problem* probs, int count, int qkv_dtype, int batch, int heads, int s_total, int heads_err,
+                         void* Q, void* K, void* V, mmdit_stream_t stream) {
+  constexpr int ROW_T = 3 * HD / 8;      // threads of a qkv row per head
   MMDIT_CHECK_ARG(Q && K && V);
   QkProb q[2] = {};
-  if (int e = qk_list(probs, count, batch, heads, s_total, 1024, false, false, nullptr, nullptr, nullptr, q)) return e;
+  if (int e = qk_list(probs, count, batch, heads, HD, s_total, 1024 / ROW_T, heads_err, false, false, nullptr, nullptr, nullptr, q)) return e;
   if (qkv_dtype != MMDIT_BF16 && qkv_dtype != MMDIT_F32) return MMDIT_ERR_DTYPE;
   int g[2] = {0, 0};
-  for (int i = 0; i < count; i++) {      // (grid and same_token restated as qk_fwd_path in tests/test_rowops_edges_gpu.py)
-    g[i] = q[i].rows < 1024 ? q[i].rows : 1024;
-    if (q[i].rcos && q[i].tokens <= 1024 && q[i].rows >= q[i].tokens) g[i] = (g[i] / q[i].tokens > 0 ? g[i] / q[i].tokens : 1) * q[i].tokens;
-  }
+  for (int i = 0; i < count; i++) g[i] = qk_grid(HD, q[i].rows, q[i].tokens, q[i].rcos != nullptr, 1024, 1);      // (same_token follows in the kernel; restated as qk_fwd_path in tests/test_rowops_edges_gpu.py)
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid(g[0] + g[1]);
-  if (qkv_dtype == MMDIT_BF16) hipLaunchKernelGGL((qk_norm_rope_fwd_kernel<bf16_t>), grid, dim3(24 * heads), 0, s, q[0], q[1], g[0], heads, s_total, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V);
-  else hipLaunchKernelGGL((qk_norm_rope_fwd_kernel<float>), grid, dim3(24 * heads), 0, s, q[0], q[1], g[0], heads, s_total, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V);
+  const dim3 grid(g[0] + g[1]), block(ROW_T * heads);
+  if (qkv_dtype == MMDIT_BF16) hipLaunchKernelGGL((qk_norm_rope_fwd_kernel<HD, bf16_t>), grid, block, 0, s, q[0], q[1], g[0], heads, s_total, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V);
+  else hipLaunchKernelGGL((qk_norm_rope_fwd_kernel<HD, float>), grid, block, 0, s, q[0], q[1], g[0], heads, s_total, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V);
   return mmdit_launch_status();
 }
 
-extern "C" int mmdit_qk_norm_rope_bwd(const mmdit_qk_problem* probs, int count, const void* dQ, const void* dK, const void* dV, int dq_dtype,
-                                      int qkv_dtype, int dqkv_dtype, int batch, int heads, int s_total, mmdit_stream_t stream) {
+template <int HD>
+static int qk_bwd_launch(const mmdit_qk_problem* probs, int count, const void* dQ, const void* dK, const void* dV, int dq_dtype,
+                         int qkv_dtype, int dqkv_dtype, int batch, int heads, int s_total, int heads_err, mmdit_stream_t stream) {
+  constexpr int ROW_T = 3 * HD / 8;
   QkProb q[2] = {};
-  if (int e = qk_list(probs, count, batch, heads, s_total, 1024, false, true, dQ, dK, dV, q)) return e;
+  if (int e = qk_list(probs, count, batch, heads, HD, s_total, 1024 / ROW_T, heads_err, false, true, dQ, dK, dV, q)) return e;
   const int combo = qk_bwd_combo(dq_dtype, qkv_dtype, dqkv_dtype);
   if (combo < 0) return MMDIT_ERR_DTYPE;
-  int rl = qk_bwd_rl(heads, count == 2 && q[1].rows < q[0].rows ? q[1].rows : q[0].rows);     // (one block shape for every problem of the list)
+  const int rl = qk_rl(ROW_T * heads, count == 2 && q[1].rows < q[0].rows ? q[1].rows : q[0].rows);     // (one block shape for every problem of the list)
   int g[2] = {0, 0};
-  bool fast = true;      // (restated as qk_bwd_path in tests/test_rowops_edges_gpu.py)
+  bool once = true;      // (restated as qk_bwd_path in tests/test_rowops_edges_gpu.py)
   for (int i = 0; i < count; i++) {
-    g[i] = qk_bwd_grid(q[i].rows, q[i].tokens, q[i].rcos != nullptr, rl);
-    fast = fast && (!q[i].rcos || (g[i] * rl) % q[i].tokens == 0);
+    g[i] = qk_grid(HD, q[i].rows, q[i].tokens, q[i].rcos != nullptr, qk_bwd_lanes(rl), rl);
+    once = once && (!q[i].rcos || (g[i] * rl) % q[i].tokens == 0);
   }
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid(g[0] + g[1]);
-#define QKL(TG, TI, TO) do { if (fast) hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<true, TG, TI, TO>), grid, dim3(24 * heads * rl), 0, s, q[0], q[1], g[0], heads, s_total); \
-  else hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<false, TG, TI, TO>), grid, dim3(24 * heads * rl), 0, s, q[0], q[1], g[0], heads, s_total); } while (0)
-  if (combo == 0) QKL(bf16_t, bf16_t, bf16_t);
-  else if (combo == 1) QKL(float, float, float);
-  else QKL(bf16_t, float, float);
+  const dim3 grid(g[0] + g[1]), block(ROW_T * heads * rl);
+#define QKL(F, TG, TI, TO) hipLaunchKernelGGL((qk_norm_rope_bwd_kernel<HD, F, TG, TI, TO>), grid, block, 0, s, q[0], q[1], g[0], heads, s_total)
+  // the factor mode per width (QkFactors): moving either width to another mode is a tuning decision nobody has measured
+#define QKF(TG, TI, TO) do { if constexpr (HD == 128) QKL(QK_PER_ROW, TG, TI, TO); else if (once) QKL(QK_ONCE, TG, TI, TO); else QKL(QK_PER_PAIR, TG, TI, TO); } while (0)
+  if (combo == 0) QKF(bf16_t, bf16_t, bf16_t);
+  else if (combo == 1) QKF(float, float, float);
+  else QKF(bf16_t, float, float);
+#undef QKF
 #undef QKL
   return mmdit_launch_status();
 }
 
+extern "C" int mmdit_qk_norm_rope_fwd(const mmdit_qk_problem* probs, int count, int qkv_dtype, int batch, int heads, int s_total,
+                                      void* Q, void* K, void* V, mmdit_stream_t stream) {
+  return qk_fwd_launch<64>(probs, count, qkv_dtype, batch, heads, s_total, MMDIT_ERR_ARG, Q, K, V, stream);
+}
+extern "C" int mmdit_qk_norm_rope_bwd(const mmdit_qk_problem* probs, int count, const void* dQ, const void* dK, const void* dV, int dq_dtype,
+                                      int qkv_dtype, int dqkv_dtype, int batch, int heads, int s_total, mmdit_stream_t stream) {
+  return qk_bwd_launch<64>(probs, count, dQ, dK, dV, dq_dtype, qkv_dtype, dqkv_dtype, batch, heads, s_total, MMDIT_ERR_ARG, stream);
+}
+// head width 128 (include/mmdit_hip_hd128.h): the same kernels with 16 lanes per head vector, a row of 48 * heads threads.  Plain, not tuned
+extern "C" int mmdit_qk_norm_rope_fwd_hd128(const mmdit_qk_problem* probs, int count, int qkv_dtype, int batch, int heads, int s_total,
+                                            void* Q, void* K, void* V, mmdit_stream_t stream) {
+  return qk_fwd_launch<128>(probs, count, qkv_dtype, batch, heads, s_total, MMDIT_ERR_SHAPE, Q, K, V, stream);
+}
+extern "C" int mmdit_qk_norm_rope_bwd_hd128(const mmdit_qk_problem* probs, int count, const void* dQ, const void* dK, const void* dV, int dq_dtype,
+                                            int qkv_dtype, int dqkv_dtype, int batch, int heads, int s_total, mmdit_stream_t stream) {
+  return qk_bwd_launch<128>(probs, count, dQ, dK, dV, dq_dtype, qkv_dtype, dqkv_dtype, batch, heads, s_total, MMDIT_ERR_SHAPE, stream);
+}
+
 // kv_merge_attn (Attention.py:243-251): see qk_merge_fwd_body.  K / V: (batch, heads, s_total / 2, 64); Q and dQ as in the plain launches.
+constexpr int QK_MERGE_MAX_HEADS = 512 / 24;      // a workgroup is one pair of 24 * heads <= 512 threads (255 VGPRs: both rows of a pair and their factors stay in registers)
 extern "C" int mmdit_qk_norm_rope_fwd_merge(const mmdit_qk_problem* probs, int count, int qkv_dtype, int batch, int heads, int s_total,
                                             void* Q, void* K, void* V, mmdit_stream_t stream) {
   MMDIT_CHECK_ARG(Q && K && V);
   QkProb q[2] = {};
-  if (int e = qk_list(probs, count, batch, heads, s_total, 512, true, false, nullptr, nullptr, nullptr, q)) return e;
+  if (int e = qk_list(probs, count, batch, heads, 64, s_total, QK_MERGE_MAX_HEADS, MMDIT_ERR_ARG, true, false, nullptr, nullptr, nullptr, q)) return e;
   if (qkv_dtype != MMDIT_BF16 && qkv_dtype != MMDIT_F32) return MMDIT_ERR_DTYPE;
   int g[2] = {0, 0};
   for (int i = 0; i < count; i++) { const int pairs = q[i].rows / 2; g[i] = pairs < 1024 ? pairs : 1024; }
@@ -1359,7 +1355,7 @@ extern "C" int mmdit_qk_norm_rope_fwd_merge(const mmdit_qk_problem* probs, int c
 extern "C" int mmdit_qk_norm_rope_bwd_merge(const mmdit_qk_problem* probs, int count, const void* dQ, const void* dK, const void* dV, int dq_dtype,
                                             int qkv_dtype, int dqkv_dtype, int batch, int heads, int s_total, mmdit_stream_t stream) {
   QkProb q[2] = {};
-  if (int e = qk_list(probs, count, batch, heads, s_total, 512, true, true, dQ, dK, dV, q)) return e;
+  if (int e = qk_list(probs, count, batch, heads, 64, s_total, QK_MERGE_MAX_HEADS, MMDIT_ERR_ARG, true, true, dQ, dK, dV, q)) return e;
   const int combo = qk_bwd_combo(dq_dtype, qkv_dtype, dqkv_dtype);
   if (combo < 0) return MMDIT_ERR_DTYPE;
   int g[2] = {0, 0};

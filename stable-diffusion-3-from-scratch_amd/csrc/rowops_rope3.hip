@@ -7,29 +7,14 @@
 // (the normalised z in the forward, the incoming gradient in the backward), and every lane gathers the (up to) three values each of ITS
 // eight output channels needs -- global reads and writes stay aligned 16-byte vectors in both directions.
 // The arithmetic around the rotation (sum of squares, rsqrt, the two norm products, the norm backward and the weight-gradient
-// accumulation) is that of qk_norm_rope_fwd_body / qk_norm_rope_bwd_body in rowops.hip.  Plain kernels, not tuned.
-#include "common.h"
+// accumulation) is that of qk_norm_rope_fwd_body / qk_norm_rope_bwd_body in rowops.hip; the problem list, its validation and the lane-group sum are
+// those kernels' (qk_rows.h).  Plain kernels, not tuned.
+#include "qk_rows.h"
 #include "../../include/mmdit_hip_rope3.h"
 
 namespace {
 
 constexpr int WG = 256;                     // threads per workgroup: WG / (HD / 8) head vectors per iteration
-constexpr float RMS_EPS = 1.1920929e-07f;   // nn.RMSNorm(eps=None) on fp32 input: finfo(float32).eps (= RMS_EPS of rowops.hip)
-
-// sum over the G = 8 or 16 lanes of a head vector (a G-aligned lane group of one wave)
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
-  v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64);
-  if (G == 16) v += __shfl_xor(v, 8, 64);
-  return v;
-}
-
-// a list of one or two problems (workgroups [0, g0) = problem 0): the image and the text rows of a block write the same Q / K / V, different token ranges
-struct QkProb {
-  const void* qkv; const float* wq; const float* wk; const float* rcos; const float* rsin; int rows, tokens, tok0;
-  const void* dQ; const void* dK; const void* dV; void* dqkv; float* dwq; float* dwk;      // (backward only)
-};
-
 // (bid, nwg) = this workgroup's index and the number of workgroups of ITS problem
 template <typename TI, int HD>
 __device__ __forceinline__ void qk3_fwd_body(int bid, int nwg, const TI* __restrict__ qkv, const float* __restrict__ wq, const float* __restrict__ wk,
@@ -98,10 +83,8 @@ __device__ __forceinline__ void qk3_fwd_body(int bid, int nwg, const TI* __restr
 template <typename TI, int HD>
 __global__ __launch_bounds__(WG) void qk3_fwd_kernel(QkProb p0, QkProb p1, int g0, int heads, int s_total,
                                                      bf16_t* __restrict__ Q, bf16_t* __restrict__ K, bf16_t* __restrict__ V) {
-  const bool first = (int)blockIdx.x < g0;     // (workgroup-uniform)
-  const QkProb& p = first ? p0 : p1;
-  qk3_fwd_body<TI, HD>(first ? (int)blockIdx.x : (int)blockIdx.x - g0, first ? g0 : (int)gridDim.x - g0, (const TI*)p.qkv, p.wq, p.wk, p.rcos, p.rsin,
-                       p.rows, p.tokens, heads, s_total, p.tok0, Q, K, V);
+  QK_SELECT(p, bid, nwg);
+  qk3_fwd_body<TI, HD>(bid, nwg, (const TI*)p.qkv, p.wq, p.wk, p.rcos, p.rsin, p.rows, p.tokens, heads, s_total, p.tok0, Q, K, V);
 }
 
 // Backward: the incoming gradient of a head vector goes through LDS (channel 3j + r needs dOut[j], dOut[T+j], dOut[2T+j]); the norm-weight
@@ -190,27 +173,11 @@ __device__ __forceinline__ void qk3_bwd_body(int bid, int nwg, const TG* __restr
 }
 template <typename TG, typename TI, typename TO, int HD>
 __global__ __launch_bounds__(WG) void qk3_bwd_kernel(QkProb p0, QkProb p1, int g0, int heads, int s_total) {
-  const bool first = (int)blockIdx.x < g0;     // (workgroup-uniform)
-  const QkProb& p = first ? p0 : p1;
-  qk3_bwd_body<TG, TI, TO, HD>(first ? (int)blockIdx.x : (int)blockIdx.x - g0, first ? g0 : (int)gridDim.x - g0, (const TG*)p.dQ, (const TG*)p.dK, (const TG*)p.dV,
-                               (const TI*)p.qkv, p.wq, p.wk, p.rcos, p.rsin, p.rows, p.tokens, heads, s_total, p.tok0, (TO*)p.dqkv, p.dwq, p.dwk);
+  QK_SELECT(p, bid, nwg);
+  qk3_bwd_body<TG, TI, TO, HD>(bid, nwg, (const TG*)p.dQ, (const TG*)p.dK, (const TG*)p.dV, (const TI*)p.qkv, p.wq, p.wk, p.rcos, p.rsin,
+                               p.rows, p.tokens, heads, s_total, p.tok0, (TO*)p.dqkv, p.dwq, p.dwk);
 }
 
-// validates the problem list (as qk_list of rowops.hip) and returns the kernel-side problems
-static inline int qk3_list(const mmdit_qk_problem* probs, int count, int batch, int heads, int head_dim, int s_total, bool bwd,
-                           const void* dQ, const void* dK, const void* dV, QkProb (&q)[2]) {
-  MMDIT_CHECK_ARG(probs && count >= 1 && count <= 2 && batch > 0 && heads > 0 && s_total > 0 && (!bwd || (dQ && dK && dV)));
-  if (head_dim != 64 && head_dim != 128) return MMDIT_ERR_SHAPE;
-  for (int i = 0; i < count; i++) {
-    const mmdit_qk_problem* p = probs + i;
-    MMDIT_CHECK_ARG(p->qkv && p->wq && p->wk && p->tokens > 0 && p->tok0 >= 0 && p->tok0 + (int64_t)p->tokens <= s_total && (p->rope_cos == nullptr) == (p->rope_sin == nullptr));
-    MMDIT_CHECK_ARG(!bwd || (p->dqkv && p->dwq && p->dwk));
-    if ((int64_t)batch * p->tokens > 0x7fffffff) return MMDIT_ERR_SHAPE;
-    q[i] = QkProb{p->qkv, p->wq, p->wk, p->rope_cos, p->rope_sin, batch * p->tokens, p->tokens, p->tok0, dQ, dK, dV,
-                  bwd ? p->dqkv : nullptr, bwd ? p->dwq : nullptr, bwd ? p->dwk : nullptr};
-  }
-  return 0;
-}
 // workgroups of one problem: one per WG / (HD / 8) head vectors, at most `wg_max` (the grid-stride loop takes the rest)
 static inline int qk3_grid(const QkProb& p, int heads, int head_dim, int wg_max) {
   const int64_t ipw = WG / (head_dim / 8), need = ((int64_t)p.rows * 3 * heads + ipw - 1) / ipw;
@@ -223,7 +190,7 @@ extern "C" int mmdit_qk_norm_rope3_fwd(const mmdit_qk_problem* probs, int count,
                                        int s_total, void* Q, void* K, void* V, mmdit_stream_t stream) {
   MMDIT_CHECK_ARG(Q && K && V);
   QkProb q[2] = {};
-  if (int e = qk3_list(probs, count, batch, heads, head_dim, s_total, false, nullptr, nullptr, nullptr, q)) return e;
+  if (int e = qk_list(probs, count, batch, heads, head_dim, s_total, 0, 0, false, false, nullptr, nullptr, nullptr, q)) return e;
   if (qkv_dtype != MMDIT_BF16 && qkv_dtype != MMDIT_F32) return MMDIT_ERR_DTYPE;
   int g[2] = {0, 0};
   for (int i = 0; i < count; i++) g[i] = qk3_grid(q[i], heads, head_dim, 2048);
@@ -239,11 +206,8 @@ extern "C" int mmdit_qk_norm_rope3_fwd(const mmdit_qk_problem* probs, int count,
 extern "C" int mmdit_qk_norm_rope3_bwd(const mmdit_qk_problem* probs, int count, const void* dQ, const void* dK, const void* dV, int dq_dtype,
                                        int qkv_dtype, int dqkv_dtype, int batch, int heads, int head_dim, int s_total, mmdit_stream_t stream) {
   QkProb q[2] = {};
-  if (int e = qk3_list(probs, count, batch, heads, head_dim, s_total, true, dQ, dK, dV, q)) return e;
-  // dtype combinations (dQ / dK / dV, saved qkv, dqkv): all bf16, all fp32, bf16 gradients of an fp32 projection -- those of mmdit_qk_norm_rope_bwd
-  const int combo = (dq_dtype == MMDIT_BF16 && qkv_dtype == MMDIT_BF16 && dqkv_dtype == MMDIT_BF16) ? 0
-                  : (dq_dtype == MMDIT_F32 && qkv_dtype == MMDIT_F32 && dqkv_dtype == MMDIT_F32)    ? 1
-                  : (dq_dtype == MMDIT_BF16 && qkv_dtype == MMDIT_F32 && dqkv_dtype == MMDIT_F32)   ? 2 : -1;
+  if (int e = qk_list(probs, count, batch, heads, head_dim, s_total, 0, 0, false, true, dQ, dK, dV, q)) return e;
+  const int combo = qk_bwd_combo(dq_dtype, qkv_dtype, dqkv_dtype);
   if (combo < 0) return MMDIT_ERR_DTYPE;
   int g[2] = {0, 0};
   for (int i = 0; i < count; i++) g[i] = qk3_grid(q[i], heads, head_dim, 512);      // (2 * head_dim global atomics per workgroup)

@@ -1,5 +1,5 @@
 """Head width 128: tile-edge sweep of the attention kernels (csrc/attention_hd128.hip) and of the QK-RMSNorm / RoPE kernels
-(csrc/rowops_hd128.hip) with per-row and per-element float64 parity through ops.* and the C ABI (include/mmdit_hip_hd128.h).
+(the HD = 128 instantiations of csrc/rowops.hip) with per-row and per-element float64 parity through ops.* and the C ABI (include/mmdit_hip_hd128.h).
 
 Attention.  Reference and yardstick are those of test_attention_edges_gpu.py, restated for a 128-wide head (SCALE = 128 ** -0.5):
 plain float64 torch attention of the bf16-rounded operands; with u = 2^-8, componentwise,
@@ -402,6 +402,9 @@ QK_CASES = [
     (17, 2, ((128, True),), 0, (0, 0)),                    # 2176 rows, 10 per workgroup, 640 lanes: 3.4 passes (off)
     (9, 3, ((256, True),), 0, (0, 0)),                     # 2304 rows, 7 per workgroup, no multiple of 256 lanes fits: general path at rl > 1
     (700, 1, ((3, False),), 1, (2, 3)),                    # 2100 rows, 21 per workgroup (1008 threads), no RoPE
+    # the two shapes at which the launch policy of width 64 runs one lane per token and this width's does not (qk_grid in csrc/rowops.hip):
+    (3, 2, ((1000, True),), 0, (0, 0)),                    # 3000 rows, 10 per workgroup; 768 lanes < 1000 tokens <= 2048, a multiple of 10: 76 workgroups, factors per row
+    (1, 2, ((600, True),), 2, (0, 0)),                     # 600 rows, one per workgroup; 512 lanes < 600 tokens <= 1024: 512 workgroups, factors per row
 ]
 
 

@@ -113,7 +113,7 @@ def test_build_lists_the_sources_and_the_header():
     spec = importlib.util.spec_from_file_location("_mmdit_build_hd128", os.path.join(os.path.dirname(L.LIB_PATH), "build.py"))
     B = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(B)
-    assert "attention_hd128.hip" in B.SOURCES and "rowops_hd128.hip" in B.SOURCES
+    assert "attention_hd128.hip" in B.SOURCES and "rowops.hip" in B.SOURCES      # (rowops.hip: the QK-norm / RoPE kernels are its HD = 128 instantiations)
     assert os.path.samefile(B.HEADER_HD128, L.HEADER_HD128_PATH)
 
 
@@ -239,3 +239,10 @@ def test_sweep_covers_the_tile_edges():
     assert any(r for c in A.QK_CASES for _, r in c[2]) and any(not r for c in A.QK_CASES for _, r in c[2])
     big = [c for c in A.QK_CASES if min(c[0] * t for t, _ in c[2]) >= A.RL_MIN_ROWS]
     assert len(big) >= 3 and any(1024 // (48 * c[1]) > 1 for c in big) and {c[3] for c in A.QK_CASES} == {0, 1, 2}
+    # the launch policy is one rule for both widths with one 64-only line (one lane per token): both of its halves, several rows per workgroup
+    # and one, are reached at 128, where the grid must stay the other one (restatement of tests/test_rowops_edges_gpu.py)
+    import test_rowops_edges_gpu as R
+    differ = {R.qk_bwd_rl(c[1], c[0] * t, hd=128) > 1 for c in A.QK_CASES for t, r in c[2] if len(c[2]) == 1
+              and R.qk_bwd_grid(c[0] * t, t, r, R.qk_bwd_rl(c[1], c[0] * t, hd=128), hd=128) != R.qk_bwd_grid(c[0] * t, t, r, R.qk_bwd_rl(c[1], c[0] * t, hd=128), hd=64)}
+    assert differ == {False, True}
+    assert R.qk_bwd_path(3, 2, ((1000, True),), hd=128)[0] == 10 and R.qk_bwd_grid(3000, 1000, True, 10, hd=128) == 76 and R.qk_bwd_grid(600, 600, True, 1, hd=128) == 512

@@ -13,10 +13,11 @@ output, eps = 1e-6 instead of 1e-5 or a one-pass variance all pass there.  This 
   the MX-emitting adaLN / SwiGLU forms                            bit-identical to "bf16 output + mmdit_mxfp8_quantize"
 
 at the smallest shapes that reach each path.  The product library has no query for the shape of a row launch, so the launch arithmetic is RESTATED
-below in pure Python (nit_for / nit_bucket, qk_bwd_rl / qk_bwd_grid / the fast rule, the forward grid and same_token, the colsum rch, the one-round
+below in pure Python (nit_for / nit_bucket, qk_rl / qk_grid / the fast rule, the forward grid and same_token, the colsum rch, the one-round
 rch of a two-problem adaLN backward) and every case carries the path it is meant to reach; tests/test_rowops_edges_cpu.py asserts on that restatement
 that every path is present.  The restatement can DRIFT from the C++ and nothing detects that: each restated launcher carries a comment that points
-here (rowops.hip: nit_for and NIT_SWITCH, ln_bwd_one_round_rch, qk_bwd_rl, qk_bwd_grid, mmdit_qk_norm_rope_fwd, mmdit_qk_norm_rope_bwd, mmdit_colsum).
+here (rowops.hip: nit_for and NIT_SWITCH, ln_bwd_one_round_rch, qk_rl, qk_bwd_lanes, qk_grid, qk_fwd_launch, qk_bwd_launch, mmdit_colsum).  The QK launch
+policy is one rule for head width 64 and 128; it is restated with the width as an argument, and this file runs it at 64 (128: tests/test_attn_hd128_gpu.py).
 
 Reference: plain float64 torch of the operands exactly as the kernel receives them (bf16 values widened, fp32 as is), no ops.* call inside; the
 backward kernels read saved statistics (mean / rstd), which the test produces in float64 and rounds to fp32 -- the reference uses those fp32 numbers
@@ -103,7 +104,7 @@ u = 2.0 ** -24
 U = 2.0 ** -8
 E23 = 2.0 ** -23
 LN_EPS = 1e-5              # rowops.hip LN_EPS
-RMS_EPS = 2.0 ** -23       # rowops.hip RMS_EPS = FLT_EPSILON
+RMS_EPS = 2.0 ** -23       # qk_rows.h RMS_EPS = FLT_EPSILON
 FLUSH = 2.0 ** -126        # smallest normal fp32: the kernels' arithmetic flushes what lies below
 ERF_ABS = 2 * 1.2726 * E23     # twice the worst |1.f + erff(x / sqrt 2) - (1 + erf)| of tools/probes/row_intrinsics_probe.hip (profiles/rowops_edge_sweep.txt)
 GUARD = 256
@@ -123,19 +124,19 @@ def ops():
 NIT_BUCKETS = (1, 2, 3, 4, 6, 9, 12, 16)
 
 
-def nit_for(d):                                   # rowops.hip:1034 nit_for
+def nit_for(d):                                   # rowops.hip:1037 nit_for
     return (d // 4 + 63) // 64
 
 
-def nit_bucket(d):                                # rowops.hip:1044-1054 NIT_SWITCH
+def nit_bucket(d):                                # rowops.hip:1047-1057 NIT_SWITCH
     return next(b for b in NIT_BUCKETS if nit_for(d) <= b)
 
 
-def ln_bwd_flush(d):                              # rowops.hip:218 ln_mod_bwd_body: `if constexpr (NIT <= 6)`
+def ln_bwd_flush(d):                              # rowops.hip:217 ln_mod_bwd_body: `if constexpr (NIT <= 6)`
     return "lds" if nit_bucket(d) <= 6 else "atomics"
 
 
-def ln_bwd_rch(probs, d, cus=256):                # rowops.hip:1133-1165 ln_bwd_one_round_rch (the occupancy query can only lower per_cu)
+def ln_bwd_rch(probs, d, cus=256):                # rowops.hip:1136-1168 ln_bwd_one_round_rch (the occupancy query can only lower per_cu)
     if len(probs) != 2:
         return 16
     per_cu = 4 if nit_for(d) <= 3 else 3 if nit_for(d) == 4 else 2
@@ -148,42 +149,40 @@ def ln_bwd_rch(probs, d, cus=256):                # rowops.hip:1133-1165 ln_bwd_
     return 16
 
 
-def qk_bwd_rl(heads, min_rows):                   # rowops.hip:1246-1252 qk_bwd_rl
-    rl = 1024 // (24 * heads)
+def qk_bwd_rl(heads, min_rows, hd=64):            # rowops.hip:1252-1258 qk_rl (row_threads = 3 * hd / 8 * heads)
+    rl = 1024 // (3 * hd // 8 * heads)
     return 1 if rl < 1 or min_rows < 2048 else rl
 
 
-def qk_bwd_grid(rows, tokens, rope, rl, lanes_max=768):      # rowops.hip:1253-1266 qk_bwd_grid
-    if rl == 1:
-        g = min(rows, 512)
-        if rope and tokens <= 1024 and rows >= tokens:
-            g = max(g // tokens, 1) * tokens
-        return g
-    if not rope:
-        return lanes_max // rl
-    if tokens > lanes_max:
-        return tokens // rl if tokens <= 2048 and tokens % rl == 0 else lanes_max // rl
-    k = lanes_max // tokens
-    while k > 1 and (k * tokens) % rl:
-        k -= 1
-    return lanes_max // rl if (k * tokens) % rl else k * tokens // rl
+def qk_grid(rows, tokens, rope, lanes_max, rl, hd=64):       # rowops.hip:1263-1273 qk_grid
+    lanes = min(rows, lanes_max)
+    if rope and tokens <= lanes:
+        k = lanes // tokens
+        while k > 1 and (k * tokens) % rl:
+            k -= 1
+        if (k * tokens) % rl == 0:
+            return k * tokens // rl
+    if hd == 64 and rope and tokens > lanes and tokens <= rows and tokens <= (2048 if rl > 1 else 1024) and tokens % rl == 0:
+        return tokens // rl
+    return max(lanes // rl, 1)
 
 
-def qk_bwd_path(batch, heads, streams):           # rowops.hip:1325-1331 mmdit_qk_norm_rope_bwd; streams: ((tokens, rope), ...) -> (rl, fast)
-    rl = qk_bwd_rl(heads, min(batch * t for t, _ in streams))
-    fast = all((not rope) or (qk_bwd_grid(batch * t, t, rope, rl) * rl) % t == 0 for t, rope in streams)
+def qk_bwd_grid(rows, tokens, rope, rl, lanes_max=768, hd=64):      # rowops.hip:1259-1262 qk_bwd_lanes, then qk_grid
+    return qk_grid(rows, tokens, rope, lanes_max if rl > 1 else 512, rl, hd)
+
+
+def qk_bwd_path(batch, heads, streams, hd=64):    # rowops.hip:1300-1306 qk_bwd_launch; streams: ((tokens, rope), ...) -> (rl, fast = QK_ONCE; width 128 runs QK_PER_ROW whatever it is)
+    rl = qk_bwd_rl(heads, min(batch * t for t, _ in streams), hd)
+    fast = all((not rope) or (qk_bwd_grid(batch * t, t, rope, rl, hd=hd) * rl) % t == 0 for t, rope in streams)
     return rl, fast
 
 
-def qk_fwd_path(batch, tokens, rope):             # rowops.hip:1307-1311 mmdit_qk_norm_rope_fwd and :406 qk_norm_rope_fwd_body -> (grid, same_token)
-    rows = batch * tokens
-    g = min(rows, 1024)
-    if rope and tokens <= 1024 and rows >= tokens:
-        g = max(g // tokens, 1) * tokens
+def qk_fwd_path(batch, tokens, rope, hd=64):      # rowops.hip:1284 qk_fwd_launch and :402 qk_norm_rope_fwd_body -> (grid, same_token)
+    g = qk_grid(batch * tokens, tokens, rope, 1024, 1, hd)
     return g, bool(rope and g % tokens == 0)
 
 
-def colsum_rch(rows):                             # rowops.hip:1501 mmdit_colsum
+def colsum_rch(rows):                             # rowops.hip:1497 mmdit_colsum
     return 8 if rows <= 256 else 64
 
 
@@ -410,7 +409,7 @@ def data_rms(c, fam):
 
 
 def qk_dtypes(combo):
-    """(dQ / dK / dV, saved qkv, dqkv) of rowops.hip qk_bwd_combo."""
+    """(dQ / dK / dV, saved qkv, dqkv) of qk_rows.h qk_bwd_combo."""
     return ((BF, BF, BF), (F32, F32, F32), (BF, F32, F32))[combo]
 
 
