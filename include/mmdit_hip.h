@@ -102,7 +102,7 @@ typedef struct {
    * NHWC bf16 tensor (batch, conv_H + 2, conv_W + 2, conv_C) and K = 9 * conv_C ordered (kh, kw, c) -- B is the weight re-laid
    * as [N][kh][kw][C].  conv_mode 1: stride 1, padding 1, M = batch * conv_H * conv_W.  conv_mode 2: stride 2 after padding
    * (0,1,0,1) (diffusers Downsample2D), M = batch * (conv_H/2) * (conv_W/2).  Output rows are the output pixels in NHWC
-   * order.  Needs bf16 operands and conv_C % 32 == 0; lda is ignored. */
+   * order.  Needs bf16 operands and conv_C % 64 == 0 (K = 9 * conv_C must be a multiple of the 64-wide K tile); lda is ignored. */
   int conv_mode, conv_H, conv_W, conv_C;
   /* fp8 operands (a_dtype == b_dtype == MMDIT_FP8, row-major, K % 128 == 0), the matrix instruction is the 64-wide
    * v_mfma_scale_f32_32x32x64_f8f6f4.

@@ -635,7 +635,8 @@ static int plan_gemm(const mmdit_gemm_args* args, int count, const QkRequest* qk
     if (a->a_kmajor && a->M < 8) dma = false;
     if (a->b_kmajor && a->N < 8) dma = false;
     if (a->conv_mode) {
-      // implicit-GEMM convolution: DMA path only (bf16, conv_C % 32 == 0 so that a K half never straddles a tap), plain row-major B
+      // implicit-GEMM convolution: DMA path only (bf16; conv_C % 32 == 0 so that a K half never straddles a tap, and K = 9 conv_C a multiple of the 64-wide
+      // K tile: together conv_C % 64 == 0 -- tests/test_gemm_edges_cpu.py pins that 32 and 96 are refused), plain row-major B
       MMDIT_CHECK_ARG((a->conv_mode == 1 || a->conv_mode == 2) && !a->a_kmajor && !a->b_kmajor && a->conv_C > 0 && a->conv_C % 32 == 0 && a->K == 9 * a->conv_C && a->K % BK == 0);
       MMDIT_CHECK_ARG(a->conv_H > 0 && a->conv_W > 0 && (a->conv_mode == 1 || (a->conv_H % 2 == 0 && a->conv_W % 2 == 0)));
       const int64_t px = a->conv_mode == 1 ? (int64_t)a->conv_H * a->conv_W : (int64_t)(a->conv_H / 2) * (a->conv_W / 2);

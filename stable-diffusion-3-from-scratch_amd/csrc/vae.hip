@@ -7,6 +7,7 @@
 
 namespace {
 
+// (restated in tests/test_vae_edges_gpu.py grid_cap / past_cap: the sweep runs every grid-stride kernel once past the 65535-block cap)
 inline int grid_cap(int64_t n, int bs) { int64_t g = (n + bs - 1) / bs; return (int)(g < 1 ? 1 : g > 65535 ? 65535 : g); }
 
 // NCHW (fp32 or bf16) -> NHWC bf16 with the channel count padded to Cp (zero fill).  One thread per (pixel, 8 channels).
@@ -82,7 +83,7 @@ __global__ void im2col3x3_kernel(const bf16_t* __restrict__ src, bf16_t* __restr
 template <typename TI>
 __global__ __launch_bounds__(256) void gn_stats_kernel(const TI* __restrict__ x, int HW, int C, int G, int rows_per_block, float* __restrict__ sums) {
   __shared__ float s[2 * 64];   // G <= 64
-  const int cg = C / 8, tx = threadIdx.x % cg, ty = threadIdx.x / cg, nty = 256 / cg;
+  const int cg = C / 8, tx = threadIdx.x % cg, ty = threadIdx.x / cg, nty = 256 / cg;   // (nty: restated in tests/test_vae_edges_gpu.py gn_nty)
   const int b = blockIdx.y;
   for (int i = threadIdx.x; i < 2 * G; i += 256) s[i] = 0.f;
   __syncthreads();
@@ -240,6 +241,7 @@ extern "C" int mmdit_vae_groupnorm(const void* x, int x_dtype, const float* gamm
   const int HW = H * W;
   // statistics: ~2048 workgroups per launch, whatever the tensor size -- every workgroup ends with 2 * groups global atomics onto the
   // batch * 2 * groups sums (at 128 rows per workgroup a 512^2 x 128 x 16 tensor made 2 M atomics onto 1024 addresses: 1.2 TB/s)
+  // (rpb and ppb are restated in tests/test_vae_edges_gpu.py gn_rpb / PPB: keep the sweep's paths in step with a change here)
   int rpb = 128;
   while ((int64_t)((HW + rpb - 1) / rpb) * batch > 2048 && rpb < HW) rpb *= 2;
   const int ppb = 128;   // pixels per apply workgroup

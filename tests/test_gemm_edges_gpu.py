@@ -12,6 +12,10 @@ This file runs every kernel family
   8-phase kernel, 320 rows (plan 387)
   weight gradient, round + split tail (418)      K tails, atomics and workspace slots, balanced tail, grouped
   8-phase e4m3 kernel (plan 258)                 per-tensor and MX scales, SwiGLU
+  implicit-GEMM 3x3 convolution                  LDS-DMA kernel at 128 x 128 (plan 0) and 256 x 256 (plan 2: the epilogues conv8 of gemm.hip refuses -- SiLU,
+                                                 bf16 output + residual, aux) and the 8-phase CONV instantiation (plan 258 with conv_mode set: bf16 + bias,
+                                                 fp32 + bias, fp32 + bias + residual), both modes, C = 64 / 128 / 192 (3 / 6 / 9 K tiles per kernel row),
+                                                 image boundaries on, before and inside tiles, H = 1, a second and third tile per workgroup, grouped
 
 at the smallest shapes that reach it, with M and N on, one before and one past a tile edge and 1 .. 5 K tiles (the two-tile prologue of the 8-phase
 loop, its clamped "request the last K tile again" stagings, the odd trailing tile), and asserts the planner's code before every launch (the product
@@ -19,7 +23,10 @@ library ignores the environment switches: a kernel is reached through shapes and
 without a GPU).
 
 Reference: plain float64 torch matmul of the operands exactly as the kernel receives them (bf16 values, e4m3 codes x scales, fp32 for the split mode),
-epilogue in float64 (_reference: no ops.* call; the e4m3 / MX quantisers run before it, their outputs are inputs).
+epilogue in float64 (_reference: no ops.* call; the e4m3 / MX quantisers run before it, their outputs are inputs).  A convolution's A is the
+zero-bordered NHWC operand (B, H + 2, W + 2, C); its float64 A (M, 9 C) is an explicit index gather written here (conv_gather: output row
+(b, yo, xo), column (kh 3 + kw) C + c reads padded pixel (s yo + kh + o, s xo + kw + o), s = 1 | 2, o = 0 | 1 for mode 1 | 2), which
+test_gemm_edges_cpu.py holds to torch.nn.functional.conv2d in float64; from there on it is the same product, epilogue and yardstick (K = 9 C).
 
 Yardstick (derived from the kernels' rounding points, not tuned).  U = 2^-8 is the unit roundoff of bf16, products of bf16 and of e4m3 operands are
 exact in fp32, an fp32 accumulation of K terms in any order errs by at most (K - 1) 2^-24 |A| |B|^T to first order; 2^-23 per term also covers
@@ -71,7 +78,7 @@ Input families (seeded; each asserts its own precondition):
             Every byte a clamped or over-wide access can touch lies inside a tensor the test allocated: this family checks values, not faults.
 random runs on every case, integer and poison where M, N or K sits one step (1 row, 8 columns) before or past a tile edge.
 
-Worst measured ratios per kernel family and input family: profiles/r09_gemm_edge_sweep.txt.
+Worst measured ratios per kernel family and input family: profiles/r09_gemm_edge_sweep.txt; the convolution families: profiles/conv_vae_edge_sweep.txt.
 """
 import ctypes
 
@@ -101,11 +108,18 @@ def ops():
 class P:
     """One problem of a launch.  lay: nt (A (M, K), B (N, K)), dgrad (B stored (K, N)), wgrad (A stored (K, M), B stored (K, N)); ab: operand format
     bf16 | split (fp32 operands, 3-term split) | e4m3 (per-tensor scales) | mx (E8M0 block scales); out: bf16 | f32; gate = rows_per_batch (implies
-    a residual); aux: None | bf16 | f32 (ACT_SWIGLU_BWD: always the bf16 INPUT [g | u])."""
+    a residual); aux: None | bf16 | f32 (ACT_SWIGLU_BWD: always the bf16 INPUT [g | u]); conv = (mode, B, H, W, C): implicit-GEMM 3x3
+    convolution, mode 1 (stride 1, padding 1) or 2 (stride 2 after padding (0, 1, 0, 1)), A the zero-bordered NHWC operand (B, H + 2, W + 2, C):
+    M = B Ho Wo and K = 9 C follow from it (PC), layout nt, bf16 operands."""
 
     def __init__(self, M, N, K, lay="nt", ab="bf16", out="bf16", bias=False, act=ACT_NONE, gate=0, residual=False, aux=None, acc=False, split_k=1,
-                 stream_k=False, dbias=False):
+                 stream_k=False, dbias=False, conv=None):
         self.M, self.N, self.K, self.lay, self.ab, self.out = M, N, K, lay, ab, out
+        self.conv = conv
+        if conv is not None:
+            mode, B, H, W, C = conv
+            assert mode in (1, 2) and (mode == 1 or (H % 2 == 0 and W % 2 == 0)) and lay == "nt" and ab == "bf16"
+            assert (M, K) == (B * (H // mode) * (W // mode), 9 * C), (M, K, conv)
         self.bias, self.act, self.gate, self.residual, self.aux, self.acc = bias, act, gate, residual or gate > 0, aux, acc
         self.split_k, self.stream_k, self.dbias = split_k, stream_k, dbias
         if act == ACT_SWIGLU_BWD:
@@ -129,6 +143,8 @@ class P:
 
     def tag(self):
         t = f"{self.M}x{self.N}x{self.K}-{self.lay}-{self.ab}-{self.out}"
+        if self.conv is not None:
+            t += "-conv{}.{}x{}x{}x{}".format(*self.conv)
         for on, s in ((self.bias, "b"), (self.act == ACT_SILU, "silu"), (self.act == ACT_SWIGLU, "swiglu"), (self.act == ACT_SWIGLU_BWD, "swiglubwd"),
                       (self.gate, f"g{self.gate}"), (self.residual and not self.gate, "r"), (self.aux and self.act != ACT_SWIGLU_BWD, f"aux{self.aux}"),
                       (self.acc, "acc"), (self.split_k > 1, f"sk{self.split_k}"), (self.stream_k, "stk"), (self.dbias, "db")):
@@ -139,9 +155,14 @@ class P:
     def is_edge(self):
         """M one row before or past a multiple of 32, or M, N or K 8 (the granularity of k-major rows and of N and K) before or past a multiple
         of 64: every tile edge of every kernel (32-row fragments and epilogue passes, 64-wide K tiles, 128 / 160-row wave tiles, 128 / 256 /
-        320-row tiles) is one."""
+        320-row tiles) is one.  A convolution is judged by the M, N and K that follow from its geometry."""
         m = self.M % 32 in (1, 31) or self.M % 64 in (8, 56)
         return m or self.N % 64 in (8, 56) or self.K % 64 in (8, 56)
+
+
+def PC(N, mode, B, H, W, C, **kw):
+    """A convolution problem: M and K from the geometry."""
+    return P(B * (H // mode) * (W // mode), N, 9 * C, conv=(mode, B, H, W, C), **kw)
 
 
 STATIC, CLAIMED, NO_WS = (True, False), (True, True), (False, False)      # (workspace registered, tile claiming on)
@@ -280,9 +301,37 @@ def _launches():
             add(L("8p " + ab, 258, P(M, N, 128, ab=ab), budget=64))
     for K in (128, 256):
         add(L("8p mx swiglu", 258, P(257, 512, K, ab="mx", bias=True, act=ACT_SWIGLU)))
+    # ---- implicit-GEMM 3x3 convolution (conv = (mode, B, H, W, C); K = 9 C: 9 / 18 / 27 K tiles, cseg_len = 3 / 6 / 9 K tiles per kernel row)
+    # ... LDS-DMA kernel, 128 x 128 tiles: one pixel, one row, one column of pixels per image, image boundaries inside the 16-row pieces
+    for N, kw in ((8, dict()), (40, dict(out="f32", bias=True))):
+        for mode, B, H, W in ((1, 1, 1, 1), (1, 3, 5, 17), (1, 1, 1, 127), (1, 3, 1, 43), (1, 2, 8, 8), (2, 2, 2, 2), (2, 3, 10, 34)):
+            add(L("conv dma128", 0, PC(N, mode, B, H, W, 64, **kw)))
+    # ... LDS-DMA kernel, 256 x 256 tiles (budget 64): the epilogues conv8 (gemm.hip) refuses -- SiLU, bf16 output + residual, aux.  (A caller
+    # split_k > 1 is refused for every convolution by plan_gemm -- test_gemm_edges_cpu.py pins that -- so the DMA cursor never starts inside a kernel row.)
+    add(L("conv dma256", 2, PC(1288, 1, 1, 29, 53, 64, bias=True, act=ACT_SILU), budget=64))                  # M = 1537; W % 8 != 0: a 16-row piece wraps image rows
+    add(L("conv dma256", 2, PC(1288, 1, 2, 24, 32, 128, bias=True, residual=True), budget=64))                # M = 1536: the image boundary on a tile boundary
+    add(L("conv dma256", 2, PC(1288, 1, 5, 1, 307, 64, out="f32", aux="bf16"), budget=64))                    # M = 1535; H = 1: every kh = 0 / 2 tap is border
+    add(L("conv dma256", 2, PC(1288, 2, 1, 58, 106, 192, residual=True), budget=64))                          # mode 2, M = 1537
+    add(L("conv dma256", 2, PC(1288, 2, 2, 48, 64, 64, out="f32", act=ACT_SILU), budget=64))                  # mode 2, M = 1536
+    add(L("conv dma256", 2, PC(1272, 1, 1, 29, 53, 128, out="f32", bias=True, aux="f32"), budget=64))
+    add(L("conv dma256", 2, PC(1280, 2, 1, 58, 106, 64, bias=True, act=ACT_SILU), budget=64))                 # (N = 1280 / 1272 need M >= 1537: 12 x 10 tiles of 128 x 128 are one round and plan as 0)
+    add(L("conv dma256", 2, [PC(1288, 1, 1, 29, 53, 64, act=ACT_SILU), PC(1288, 1, 1, 1, 257, 128, act=ACT_SILU)], budget=64))      # grouped: C and W differ
+    # ... 8-phase kernel, CONV instantiation (budget 64): bf16 + bias, fp32 + bias, fp32 + bias + residual
+    e_bf, e_f, e_fr = dict(bias=True), dict(out="f32", bias=True), dict(out="f32", bias=True, residual=True)
+    for mode, B, H, W, C, N, kw in ((1, 1, 29, 53, 64, 1288, e_bf), (1, 1, 29, 53, 128, 1280, e_f), (1, 1, 29, 53, 192, 1272, e_fr),      # M = 1537
+                                    (2, 1, 58, 106, 128, 1272, e_bf), (2, 1, 58, 106, 192, 1288, e_f), (2, 1, 58, 106, 64, 1280, e_fr),
+                                    (1, 2, 24, 32, 64, 1288, e_f), (2, 2, 48, 64, 64, 1288, e_fr), (1, 2, 24, 32, 192, 1288, e_bf),       # M = 1536
+                                    (1, 5, 1, 307, 64, 1288, e_bf), (2, 5, 2, 614, 128, 1288, e_f), (1, 5, 1, 307, 128, 1288, e_fr),      # M = 1535; H = 1
+                                    (1, 1, 1, 1567, 64, 1288, e_bf), (1, 3, 1, 523, 64, 1288, e_f),                                       # M = 1567 / 1569: the 32-row epilogue pass
+                                    (1, 1, 1, 1663, 64, 1288, e_fr), (2, 5, 18, 74, 64, 1288, e_bf),                                      # M = 1663 / 1665: the 128-row wave tile
+                                    (1, 3, 3, 313, 64, 2056, e_bf), (1, 3, 3, 313, 128, 2056, e_fr), (2, 3, 6, 626, 192, 2056, e_f)):     # M = 2817: 108 tiles on 64 workgroups
+        add(L("conv 8p", 258, PC(N, mode, B, H, W, C, **kw), budget=64))
+    add(L("conv 8p", 258, [PC(1288, 1, 1, 29, 53, 64, bias=True), PC(1288, 1, 1, 1, 257, 128, bias=True)], budget=64))              # grouped: C and W differ in one grid
+    add(L("conv 8p", 258, [PC(1288, 2, 1, 58, 106, 128, **e_fr), PC(520, 1, 3, 5, 17, 64, **e_fr)], budget=64))
     return out
 
 
+CONV_FAMILIES = ("conv dma128", "conv dma256", "conv 8p")
 LAUNCHES = _launches()
 CASES = [(l, "random") for l in LAUNCHES] + [(l, f) for f in ("integer", "poison") for l in LAUNCHES if l.is_edge()]
 
@@ -321,6 +370,8 @@ def fake_args(GemmArgs, launch):
             a.scale_a, a.scale_b, a.scale_mode = ptr(), ptr(), int(p.ab == "mx")
         if p.dbias:
             a.dbias = ptr()
+        if p.conv is not None:      # (lda is ignored by the kernels and set to K, as ops._fill_gemm does)
+            a.conv_mode, a.conv_H, a.conv_W, a.conv_C = p.conv[0], p.conv[2], p.conv[3], p.conv[4]
         a.cu_budget = launch.budget
     return arr
 
@@ -385,6 +436,36 @@ class Out:
         return [tuple(i) for i in d.nonzero()[:8].tolist()], int(d.sum())
 
 
+def conv_gather(xp, mode):
+    """The implicit GEMM's A (M, 9 C) from the zero-bordered operand xp (B, H + 2, W + 2, C), by index: output row (b, yo, xo), column
+    (kh 3 + kw) C + c = padded pixel (s yo + kh + o, s xo + kw + o) with s = 1, o = 0 (mode 1) or s = 2, o = 1 (mode 2)."""
+    B, Hp, Wp, C = xp.shape
+    s, o = (1, 0) if mode == 1 else (2, 1)
+    Ho, Wo = (Hp - 2) // s, (Wp - 2) // s
+    yo, xo = torch.arange(Ho, device=xp.device), torch.arange(Wo, device=xp.device)
+    taps = []
+    for kh in range(3):
+        for kw in range(3):
+            yi, xi = s * yo + kh + o, s * xo + kw + o
+            taps.append(xp[:, yi[:, None], xi[None, :], :])              # (B, Ho, Wo, C)
+    return torch.stack(taps, 3).reshape(B * Ho * Wo, 9 * C)
+
+
+def conv_operand(p, x, poison):
+    """x (B, H, W, C) bf16 -> the zero-bordered operand (B, H + 2, W + 2, C) the kernel receives: dense, border exactly zero in every family;
+    poison: a view into a larger NaN tensor with GUARD spare NaN pixel rows behind (the clamped re-read min(m, M - 1) stays inside the operand)."""
+    mode, B, H, W, C = p.conv
+    n = B * (H + 2) * (W + 2) * C
+    big = torch.full((n + (GUARD * C if poison else 0),), float("nan") if poison else 0.0, dtype=torch.bfloat16, device=x.device)
+    xp = big[:n].view(B, H + 2, W + 2, C)
+    xp.zero_()
+    xp[:, 1:-1, 1:-1] = x
+    border = xp.clone()
+    border[:, 1:-1, 1:-1] = 0
+    assert int((border.view(torch.int16) != 0).sum()) == 0 and (not poison or bool(torch.isnan(big[n:].float()).all()))
+    return xp
+
+
 def _seed(p, idx):
     return 1000003 * p.M + 1009 * p.N + 17 * p.K + 7 * idx + 1
 
@@ -397,10 +478,15 @@ def build(p, family, idx, device, ops=None):
     rn = lambda *s: torch.randn(*s, generator=g)                                      # noqa: E731
     ri = lambda lo, hi, *s: torch.randint(lo, hi + 1, s, generator=g).float()         # noqa: E731
     val = (lambda *s: ri(-3, 3, *s)) if integer else rn
-    A, B = val(p.M, p.K), val(p.N, p.K)
+    A, B = (val(*p.conv[1:]) if p.conv is not None else val(p.M, p.K)), val(p.N, p.K)
     t = dict(unit=1.0)
     kw = {}
-    if p.ab in ("bf16", "split"):
+    if p.conv is not None:
+        A, B = conv_operand(p, A.to(torch.bfloat16).to(device), poison), B.to(torch.bfloat16).to(device)
+        t["A64"], t["B64"] = conv_gather(A.double(), p.conv[0]), B.double()
+        assert tuple(t["A64"].shape) == (p.M, p.K)
+        kw["conv"] = (p.conv[0],) + tuple(p.conv[2:])
+    elif p.ab in ("bf16", "split"):
         dt = torch.bfloat16 if p.ab == "bf16" else torch.float32
         A, B = A.to(dt).to(device), B.to(dt).to(device)
         t["A64"], t["B64"] = A.double(), B.double()
@@ -440,7 +526,7 @@ def build(p, family, idx, device, ops=None):
         t["unit"] = 2.0 ** -4
     if p.ab == "e4m3":
         t["unit"] = 1.0          # (scales 0.5 * 4: every product an even integer)
-    kw["A"] = _place(A.t() if p.a_km else A, poison)
+    kw["A"] = A if p.conv is not None else _place(A.t() if p.a_km else A, poison)
     kw["B"] = _place(B.t() if p.b_km else B, poison)
     kw.update(a_kmajor=p.a_km, b_kmajor=p.b_km, act=p.act, split_k=p.split_k, stream_k=p.stream_k, accumulate=p.acc)
     t["bias"] = t["gate_rows"] = t["res"] = t["cin"] = t["gu"] = None
