@@ -19,6 +19,7 @@ HEADER_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip.h")
 HEADER_EXT_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_ext.h")   # opt-in entry points outside the versioned core ABI
 HEADER_HD128_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_hd128.h")   # the head-width-128 entry points, outside it as well
 HEADER_ROPE3_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_rope3.h")   # the RoPE2dV2 entry points, outside it as well
+HEADER_QKHALF_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_qkhalf.h")   # the qk_half_dim entry points, outside it as well
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_SILU, ACT_SWIGLU, ACT_SWIGLU_BWD = 0, 1, 2, 3
@@ -160,6 +161,16 @@ _ROPE3_SIGNATURES = {
     "mmdit_qk_norm_rope3_fwd": ([ctypes.POINTER(QkProblem), _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "mmdit_qk_norm_rope3_bwd": ([ctypes.POINTER(QkProblem), _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
 }
+# entry points of include/mmdit_hip_qkhalf.h (qk_half_dim=True: 32-wide queries / keys, 64-wide values): the attention launches take the
+# argument lists of their core namesakes, the QK-norm / RoPE launches those of the plain ones with (qk_dim, v_dim) after heads
+_QKHALF_SIGNATURES = {
+    "mmdit_attn_fwd_qkhalf": _SIGNATURES["mmdit_attn_fwd"],
+    "mmdit_attn_bwd_qkhalf": _SIGNATURES["mmdit_attn_bwd"],
+    "mmdit_qk_norm_rope_fwd_qkhalf": ([ctypes.POINTER(QkProblem), _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "mmdit_qk_norm_rope_bwd_qkhalf": ([ctypes.POINTER(QkProblem), _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
+}
+QKHALF_QK_DIM, QKHALF_V_DIM = 32, 64                   # MMDIT_QKHALF_QK_DIM / MMDIT_QKHALF_V_DIM
+ATTN_QKHALF_KEY_TILE, ATTN_QKHALF_QUERY_TILE = 32, 128   # MMDIT_ATTN_QKHALF_KEY_TILE / MMDIT_ATTN_QKHALF_QUERY_TILE
 HEAD_DIMS = (64, 128)                                  # head widths the attention and QK-norm / RoPE kernels are built for
 ADAMW_CHUNK = 65536   # MMDIT_ADAMW_CHUNK
 ABI_VERSION = 10      # MMDIT_ABI_VERSION of include/mmdit_hip.h this binding mirrors
@@ -198,6 +209,13 @@ def declared_rope3_symbols():
     return sorted(set(re.findall(r"\b(mmdit_[a-z0-9_]+)\s*\(", txt)) - {"mmdit_stream_t"})
 
 
+def declared_qkhalf_symbols():
+    """Entry points declared by include/mmdit_hip_qkhalf.h (parsed the same way)."""
+    with open(HEADER_QKHALF_PATH) as f:
+        txt = f.read()
+    return sorted(set(re.findall(r"\b(mmdit_[a-z0-9_]+)\s*\(", txt)) - {"mmdit_stream_t"})
+
+
 def lib():
     """Load the HIP library (once).  Raises RuntimeError if it is not built."""
     global _lib
@@ -215,7 +233,8 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        for name, (argtypes, restype) in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_HD128_SIGNATURES.items()) + list(_ROPE3_SIGNATURES.items()):
+        for name, (argtypes, restype) in (list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_HD128_SIGNATURES.items()) + list(_ROPE3_SIGNATURES.items())
+                                          + list(_QKHALF_SIGNATURES.items())):
             fn = getattr(L, name)  # AttributeError -> symbol missing: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

@@ -1,11 +1,15 @@
 """Joint image+text attention: mirror of the reference's src/blocks/Attention.py for the trained
 configuration (dual stream, attn_type softmax / softmax_flash, RoPE2d or RoPE2dV2, non-causal; ctor 16-114,
 forward 118-135, 174-194, 220-239, 258-293, 410-425).  Experimental attention types of the reference
-(cosine*, relu, silu, exp, both, qk_half_dim, 1-D RoPE) are out of scope and
+(cosine*, relu, silu, exp, both, 1-D RoPE) are out of scope and
 raise.  positional_encoding="RoPE2dV2" (rotary_embedding_2d_v2.RoPE2D: channel triples rotated by a row and a column angle) runs on the unfused
 route: plain QKV GEMM, mmdit_qk_norm_rope3_fwd / _bwd (include/mmdit_hip_rope3.h), attention; no kv_merge_attn, no fp8 / mxfp8.  kv_merge_attn (243-251) is implemented: the keys / values of adjacent token pairs of each stream are
 averaged (mmdit_qk_norm_rope_fwd_merge) and S queries attend to S / 2 keys (mmdit_attn_fwd_kv).
-Head width dim / num_heads: 64 (every fused and e4m3 form) or 128 (the plain kernels of include/mmdit_hip_hd128.h; no kv_merge_attn)."""
+Head width dim / num_heads: 64 (every fused and e4m3 form) or 128 (the plain kernels of include/mmdit_hip_hd128.h; no kv_merge_attn).
+qk_half_dim (33-67): queries and keys are projected to dim / 2 -- with dim = 64 * num_heads a head has 32-wide queries / keys (RMSNorm(32),
+RotaryEmbedding(16)) and 64-wide values at scale 64 ** -0.5 -- and the block runs on the unfused route: plain QKV GEMM with N = 2 * dim,
+mmdit_qk_norm_rope_fwd_qkhalf / _bwd_qkhalf, mmdit_attn_fwd_qkhalf / _bwd_qkhalf (include/mmdit_hip_qkhalf.h); RoPE2d and head width 64 only, no
+kv_merge_attn, no fp8 / mxfp8."""
 from types import SimpleNamespace as NS
 
 import torch
@@ -30,8 +34,13 @@ class _AttentionFn(torch.autograd.Function):
         xa, ca = m.act(x.reshape(B * N, d).contiguous()), m.act(c.reshape(B * Mt, d).contiguous())
         qkv_x = ops.gemm(xa, w.Wqkv_x, out_dtype=m.T, precision=m.prec)
         qkv_c = ops.gemm(ca, w.Wqkv_c, out_dtype=m.T, precision=m.prec)
-        Q = torch.empty((B, H, S, mod.head_dim), dtype=BF16, device=dev)
-        if mod.rope3:
+        Q = torch.empty((B, H, S, mod.head_dim_qk), dtype=BF16, device=dev)
+        if mod.qk_half_dim:
+            K, V = torch.empty_like(Q), torch.empty((B, H, S, mod.head_dim), dtype=BF16, device=dev)
+            ops.qk_norm_rope_fwd_qkhalf(qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], B, N, H, S, 0, Q, K, V)
+            ops.qk_norm_rope_fwd_qkhalf(qkv_c, w.wq_c, w.wk_c, None, None, B, Mt, H, S, N, Q, K, V)
+            Ox, Oc, lse = ops.attn_fwd_qkhalf(Q, K, V, N, mod.scale, m.attn_mode)
+        elif mod.rope3:
             K, V = torch.empty_like(Q), torch.empty_like(Q)
             ops.qk_norm_rope3_fwd(qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], B, N, H, S, 0, Q, K, V)
             ops.qk_norm_rope3_fwd(qkv_c, w.wq_c, w.wk_c, None, None, B, Mt, H, S, N, Q, K, V)
@@ -74,8 +83,12 @@ class _AttentionFn(torch.autograd.Function):
             dac = m.act(doc.reshape(B * Mt, d).contiguous())
             dOc = ops.gemm(dac, w.Wo_c, b_kmajor=True, out_dtype=BF16, precision=m.prec)
             mod._po_c.split_grad(ops.gemm(dac, Oca, a_kmajor=True, b_kmajor=True, out_dtype=F32, precision=m.prec), gout)
-        gq_x, gk_x, gq_c, gk_c = [torch.zeros(mod.head_dim, dtype=F32, device=dev) for _ in range(4)]
-        if mod.rope3:
+        gq_x, gk_x, gq_c, gk_c = [torch.zeros(mod.head_dim_qk, dtype=F32, device=dev) for _ in range(4)]
+        if mod.qk_half_dim:
+            dQ, dK, dV = ops.attn_bwd_qkhalf(Q, K, V, Ox, Oc, dOx, dOc, lse, N, mod.scale, m.T)
+            dqkv_x = ops.qk_norm_rope_bwd_qkhalf(dQ, dK, dV, qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], B, N, H, S, 0, gq_x, gk_x, m.T)
+            dqkv_c = ops.qk_norm_rope_bwd_qkhalf(dQ, dK, dV, qkv_c, w.wq_c, w.wk_c, None, None, B, Mt, H, S, N, gq_c, gk_c, m.T)
+        elif mod.rope3:
             dQ, dK, dV = ops.attn_bwd(Q, K, V, Ox, Oc, dOx, dOc, lse, N, mod.scale, m.T)
             dqkv_x = ops.qk_norm_rope3_bwd(dQ, dK, dV, qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], B, N, H, S, 0, gq_x, gk_x, m.T)
             dqkv_c = ops.qk_norm_rope3_bwd(dQ, dK, dV, qkv_c, w.wq_c, w.wk_c, None, None, B, Mt, H, S, N, gq_c, gk_c, m.T)
@@ -102,7 +115,7 @@ class Attention(nn.Module):
         super().__init__()
         if attn_type not in ("softmax", "softmax_flash"):
             raise RuntimeError(f"attn_type must be 'softmax' or 'softmax_flash' on the HIP path, but got {attn_type}")
-        if not dual or causal or qk_half_dim or emb_dim is not None:
+        if not dual or causal or emb_dim is not None:
             raise RuntimeError("Attention: only the dual-stream, non-causal configuration of the trained model is implemented")
         if positional_encoding not in ("RoPE2d", "RoPE2dV2"):
             raise RuntimeError("Attention: only positional_encoding='RoPE2d' and 'RoPE2dV2' are implemented")
@@ -114,20 +127,31 @@ class Attention(nn.Module):
         if kv_merge_attn and positional_encoding == "RoPE2dV2":
             raise RuntimeError("Attention: kv_merge_attn is not built for positional_encoding='RoPE2dV2' (the pair-averaging kernels "
                                "mmdit_qk_norm_rope_*_merge rotate channel pairs; mmdit_qk_norm_rope3_* has no merging form)")
+        if qk_half_dim and kv_merge_attn:
+            raise RuntimeError("Attention: qk_half_dim is not built with kv_merge_attn (the pair-averaging kernels mmdit_qk_norm_rope_*_merge / mmdit_attn_*_kv "
+                               "take 64-wide queries and keys; mmdit_qk_norm_rope_*_qkhalf has no merging form)")
+        if qk_half_dim and positional_encoding == "RoPE2dV2":
+            raise RuntimeError("Attention: qk_half_dim is not built for positional_encoding='RoPE2dV2' (mmdit_qk_norm_rope3_* rotates channel triples of 64- "
+                               "or 128-wide heads; mmdit_qk_norm_rope_*_qkhalf rotates pairs)")
+        if qk_half_dim and dim // num_heads != 64:
+            raise RuntimeError(f"Attention: qk_half_dim is built for dim = 64 * num_heads only (32-wide queries / keys, 64-wide values: "
+                               f"include/mmdit_hip_qkhalf.h), but got dim={dim}, num_heads={num_heads}")
         self.rope3 = positional_encoding == "RoPE2dV2"
+        self.qk_half_dim = bool(qk_half_dim)
+        dim_qk = dim // 2 if qk_half_dim else dim      # (Attention.py:33)
         self.positional_encoding, self.kv_merge_attn, self.RoPE_Scale = positional_encoding, kv_merge_attn, RoPE_Scale
         self.layer_idx, self.dual, self.last = layer_idx, dual, last
-        self.query_proj_x = nn.Linear(dim, dim, bias=False)
-        self.key_proj_x = nn.Linear(dim, dim, bias=False)
+        self.query_proj_x = nn.Linear(dim, dim_qk, bias=False)
+        self.key_proj_x = nn.Linear(dim, dim_qk, bias=False)
         self.value_proj_x = nn.Linear(dim, dim, bias=False)
         self.out_proj_x = nn.Linear(dim, dim, bias=False)
-        self.query_proj_c = nn.Linear(dim, dim, bias=False)
-        self.key_proj_c = nn.Linear(dim, dim, bias=False)
+        self.query_proj_c = nn.Linear(dim, dim_qk, bias=False)
+        self.key_proj_c = nn.Linear(dim, dim_qk, bias=False)
         self.value_proj_c = nn.Linear(dim, dim, bias=False)
         if not self.last:
             self.out_proj_c = nn.Linear(dim, dim, bias=False)
         self.dim, self.num_heads = dim, num_heads
-        self.head_dim_qk = self.head_dim = dim // num_heads
+        self.head_dim_qk, self.head_dim = dim_qk // num_heads, dim // num_heads
         self.scale = self.head_dim ** -0.5
         self.q_norm_x = nn.RMSNorm(self.head_dim_qk)
         self.k_norm_x = nn.RMSNorm(self.head_dim_qk)
@@ -161,7 +185,8 @@ class Attention(nn.Module):
         return NS(Wqkv_x=self._pqkv_x.get(m), Wqkv_c=self._pqkv_c.get(m), Wo_x=self._po_x.get(m),
                   Wo_c=None if self.last else self._po_c.get(m),
                   wq_x=self.q_norm_x.weight.detach(), wk_x=self.k_norm_x.weight.detach(),
-                  wq_c=self.q_norm_c.weight.detach(), wk_c=self.k_norm_c.weight.detach(), kv_merge=bool(self.kv_merge_attn), hd=self.head_dim, rope3=self.rope3)
+                  wq_c=self.q_norm_c.weight.detach(), wk_c=self.k_norm_c.weight.detach(), kv_merge=bool(self.kv_merge_attn), hd=self.head_dim, rope3=self.rope3,
+                  qk_half=self.qk_half_dim)
 
     def scatter_grads(self, g, out: dict):
         self._pqkv_x.split_grad(g.Wqkv_x, out)

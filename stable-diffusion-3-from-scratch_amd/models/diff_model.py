@@ -5,7 +5,9 @@ sample_imgs (368), saveModel / loadModel checkpoint layout (489-578), state_dict
 registration order and behavioural quirks (in-place null masking of the caller's c / c_pooled,
 JSON always records device "cpu", attn_type string preserved).  positional_encoding is "RoPE2d" (the trained
 configuration) or "RoPE2dV2" (blocks/rotary_embedding_2d_v2.py: `rotary_emb.inv_freq` buffers in place of the `rotary_emb.freqs`
-parameters; "fast" / "parity" precision, no kv_merge_attn); the other three values of the reference raise.  The arithmetic of forward() and of
+parameters; "fast" / "parity" precision, no kv_merge_attn); the other three values of the reference raise.  qk_half_dim=True (queries and
+keys projected to dim / 2: 32-wide query / key heads, 64-wide values; include/mmdit_hip_qkhalf.h) is built for dim = 64 * num_heads with
+"RoPE2d" at "fast" / "parity" precision; with kv_merge_attn, "RoPE2dV2", dim = 128 * num_heads or fp8 / mxfp8 it raises.  The arithmetic of forward() and of
 its backward runs in libmmdit_hip.so through sd3_amd.engine; there is no PyTorch/CPU fallback.
 """
 import json
@@ -63,7 +65,8 @@ class _MMDiTFn(torch.autograd.Function):
 class diff_model(nn.Module):
     # inCh - number of latent channels; class_dim - pooled text embedding width; patch_size - 2;
     # dim / hidden_scale / num_heads / num_blocks - transformer geometry (dim = 64*num_heads, or 128*num_heads);
-    # attn_type - "softmax" | "softmax_flash"; MLP_type - "swiglu" | "gelu"; positional_encoding - "RoPE2d" | "RoPE2dV2"
+    # attn_type - "softmax" | "softmax_flash"; MLP_type - "swiglu" | "gelu"; positional_encoding - "RoPE2d" | "RoPE2dV2";
+    # qk_half_dim - queries / keys projected to dim / 2 (dim = 64*num_heads, "RoPE2d", no kv_merge_attn)
     def __init__(self, inCh, class_dim, patch_size, dim, hidden_scale, num_heads, attn_type, MLP_type, num_blocks, device, positional_encoding,
                  max_res_orig=256, max_res=256, update_max_res=False, kv_merge_attn=False, qk_half_dim=False, text_loss=False,
                  checkpoint_MLP=True, checkpoint_attn=True, start_step=0, wandb_id=None):
@@ -76,11 +79,21 @@ class diff_model(nn.Module):
 
         assert positional_encoding in ["absolute", "RoPE", "NoPE", "RoPE2d", "RoPE2dV2"], "positional_encoding must be 'absolute', 'RoPE', or 'NoPE' or 'RoPE2d' or 'RoPE2dV2'"
         assert MLP_type in ["gelu", "swiglu", "swiglu_old"]
-        if positional_encoding not in ("RoPE2d", "RoPE2dV2") or text_loss or qk_half_dim or MLP_type == "swiglu_old":
+        if positional_encoding not in ("RoPE2d", "RoPE2dV2") or text_loss or MLP_type == "swiglu_old":
             raise RuntimeError("diff_model (HIP path): only the trained configuration is implemented: positional_encoding='RoPE2d' (or 'RoPE2dV2'), "
-                               "MLP_type in {'swiglu','gelu'}, text_loss=False, qk_half_dim=False")
+                               "MLP_type in {'swiglu','gelu'}, text_loss=False")
         self.kv_merge_attn = bool(kv_merge_attn)
+        self.qk_half_dim = bool(qk_half_dim)
         self.positional_encoding = positional_encoding
+        if self.qk_half_dim and self.kv_merge_attn:
+            raise RuntimeError("diff_model (HIP path): qk_half_dim is not built with kv_merge_attn (the pair-averaging kernels take 64-wide queries and "
+                               "keys); use one of the two options")
+        if self.qk_half_dim and positional_encoding == "RoPE2dV2":
+            raise RuntimeError("diff_model (HIP path): qk_half_dim is not built for positional_encoding='RoPE2dV2' (mmdit_qk_norm_rope3_fwd / _bwd rotate "
+                               "channel triples of 64- or 128-wide heads); use 'RoPE2d' with qk_half_dim")
+        if self.qk_half_dim and (dim % num_heads or dim // num_heads != 64):
+            raise RuntimeError(f"diff_model (HIP path): qk_half_dim is built for dim = 64 * num_heads only (32-wide queries / keys, 64-wide values), "
+                               f"but got dim={dim}, num_heads={num_heads}")
         if self.kv_merge_attn and positional_encoding == "RoPE2dV2":
             raise RuntimeError("diff_model (HIP path): kv_merge_attn is not built for positional_encoding='RoPE2dV2' (no pair-averaging form of "
                                "mmdit_qk_norm_rope3_fwd / _bwd); use 'RoPE2d' with kv_merge_attn, or RoPE2dV2 without it")
@@ -174,6 +187,9 @@ class diff_model(nn.Module):
         if precision in ("fp8", "mxfp8") and self.positional_encoding == "RoPE2dV2":
             raise RuntimeError(f"set_precision('{precision}'): positional_encoding='RoPE2dV2' has no e4m3 path (the QKV epilogue that feeds the e4m3 / MX "
                                "attention rotates channel pairs); use 'fast' or 'parity'")
+        if precision in ("fp8", "mxfp8") and self.qk_half_dim:
+            raise RuntimeError(f"set_precision('{precision}'): qk_half_dim has no e4m3 path (the QKV epilogue, mmdit_attn_fwd_mx and mmdit_attn_fwd_e4m3 take "
+                               "64-wide queries and keys); use 'fast' or 'parity'")
         if attention not in ("bf16", "e4m3"):
             raise ValueError(f"set_precision: attention must be 'bf16' or 'e4m3', got {attention!r}")
         if attention == "e4m3" and precision not in ("fp8", "mxfp8"):

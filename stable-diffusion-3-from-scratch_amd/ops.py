@@ -741,6 +741,128 @@ def qk_norm_rope3_bwd_pair(dQ, dK, dV, img, txt, batch, heads, s_total, out_dtyp
     return _qk_rope3("mmdit_qk_norm_rope3_bwd", [img, txt], batch, heads, s_total, (dQ, dK, dV), out_dtype)
 
 
+def _qk_half(fn, streams, batch, heads, s_total, T3, out_dtype=None):
+    """One launch of a qk_half_dim row kernel (include/mmdit_hip_qkhalf.h) over a list of 1 or 2 streams -- the tuples of _qk.  T3 = (Q, K, V) of a
+    forward, (dQ, dK, dV) of a backward: the first two 32 wide, the third 64 wide.  The row width heads * (32 + 32 + 64), the norm-weight
+    length and the table width (tokens, 32) are checked here, before the launch: the kernel indexes all of them by these widths."""
+    dq, dv = _lib.QKHALF_QK_DIM, _lib.QKHALF_V_DIM
+    bwd = out_dtype is not None
+    for t, hd in zip(T3, (dq, dq, dv)):
+        if tuple(t.shape) != (batch, heads, s_total, hd) or t.dtype != T3[0].dtype or (not bwd and t.dtype != torch.bfloat16):
+            raise RuntimeError(f"{fn}: {'dQ / dK / dV' if bwd else 'Q / K / V (bfloat16)'} are (batch, heads, s_total, {dq} | {dq} | {dv}) with (batch, heads, s_total) = "
+                               f"{(batch, heads, s_total)}, of one dtype; got {t.dtype} {tuple(t.shape)}")
+        _c(t)
+    if bwd and (T3[0].dtype not in (torch.bfloat16, torch.float32) or out_dtype not in (torch.bfloat16, torch.float32)):
+        raise RuntimeError(f"{fn}: dQ / dK / dV and dqkv are bfloat16 or float32, got {T3[0].dtype} and {out_dtype}")
+    probs, outs = (_lib.QkProblem * len(streams))(), []
+    if len(streams) not in (1, 2):
+        raise RuntimeError(f"{fn}: a launch takes 1 or 2 streams, got {len(streams)}")
+    for q, st in zip(probs, streams):
+        qkv, wq, wk, rc, rs, tokens, tok0 = st[:7]
+        if qkv.dim() != 2 or tuple(qkv.shape) != (batch * tokens, heads * (2 * dq + dv)) or wq.numel() != dq or wk.numel() != dq:
+            raise RuntimeError(f"{fn}: qkv rows are (batch * tokens, heads * ({dq} + {dq} + {dv})) = {(batch * tokens, heads * (2 * dq + dv))}, norm weights {dq} wide; "
+                               f"got {tuple(qkv.shape)}, {wq.numel()}, {wk.numel()}")
+        if qkv.dtype not in (torch.bfloat16, torch.float32):
+            raise RuntimeError(f"{fn}: qkv rows are bfloat16 or float32, got {qkv.dtype}")
+        if (rc is None) != (rs is None):
+            raise RuntimeError(f"{fn}: the cos and the sin table come together (or neither: the text stream)")
+        for tb in (rc, rs):
+            if tb is not None and (tuple(tb.shape) != (tokens, dq) or tb.dtype != torch.float32):
+                raise RuntimeError(f"{fn}: the RoPE tables are fp32 (tokens, {dq}) = {(tokens, dq)}, got {tb.dtype} {tuple(tb.shape)}")
+            if tb is not None:
+                _c(tb)
+        if tokens < 1 or tok0 < 0 or tok0 + tokens > s_total:
+            raise RuntimeError(f"{fn}: tokens [{tok0}, {tok0 + tokens}) are outside the joint sequence of {s_total}")
+        if wq.dtype != torch.float32 or wk.dtype != torch.float32:
+            raise RuntimeError(f"{fn}: the norm weights are fp32")
+        q.qkv, q.wq, q.wk, q.rope_cos, q.rope_sin, q.tokens, q.tok0 = _p(_c(qkv)), _p(_c(wq)), _p(_c(wk)), _p(rc), _p(rs), tokens, tok0
+        if bwd:
+            if any(t.numel() != dq or t.dtype != torch.float32 for t in st[7:9]):
+                raise RuntimeError(f"{fn}: dwq / dwk are {dq} fp32 values")
+            dqkv = torch.empty(qkv.shape, dtype=out_dtype, device=qkv.device)
+            q.dqkv, q.dwq, q.dwk = _p(dqkv), _p(_c(st[7])), _p(_c(st[8]))
+            outs.append(dqkv)
+    if any(st[0].dtype != streams[0][0].dtype for st in streams):
+        raise RuntimeError(f"{fn}: the streams of one launch share the qkv dtype")
+    a, b, c = (_p(t) for t in T3)
+    launch, qkv_dt = getattr(_lib.lib(), fn), _dt(streams[0][0])
+    if not bwd:
+        check(launch(probs, len(streams), qkv_dt, batch, heads, dq, dv, s_total, a, b, c, _s()), fn)
+    else:
+        check(launch(probs, len(streams), a, b, c, _dt(T3[0]), qkv_dt, _DT[out_dtype], batch, heads, dq, dv, s_total, _s()), fn)
+    return outs
+
+
+def qk_norm_rope_fwd_qkhalf(qkv, wq, wk, rope_cos, rope_sin, batch, tokens, heads, s_total, tok0, Q, K, V):
+    """qk_half_dim=True: per-head RMSNorm(32) + axial RoPE + head split of one stream whose rows are [q heads*32 | k heads*32 | v heads*64]
+    (mmdit_qk_norm_rope_fwd_qkhalf); rope_cos / rope_sin = RotaryEmbedding(16).tables() (tokens, 32), or None for the text stream."""
+    _qk_half("mmdit_qk_norm_rope_fwd_qkhalf", [(qkv, wq, wk, rope_cos, rope_sin, tokens, tok0)], batch, heads, s_total, (Q, K, V))
+
+
+def qk_norm_rope_bwd_qkhalf(dQ, dK, dV, qkv, wq, wk, rope_cos, rope_sin, batch, tokens, heads, s_total, tok0, dwq, dwk, out_dtype):
+    return _qk_half("mmdit_qk_norm_rope_bwd_qkhalf", [(qkv, wq, wk, rope_cos, rope_sin, tokens, tok0, dwq, dwk)], batch, heads, s_total, (dQ, dK, dV), out_dtype)[0]
+
+
+def qk_norm_rope_fwd_qkhalf_pair(img, txt, batch, heads, s_total, Q, K, V):
+    """The image and the text rows of a qk_half_dim block in one launch; the argument tuples of qk_norm_rope_fwd_pair."""
+    _qk_half("mmdit_qk_norm_rope_fwd_qkhalf", [img, txt], batch, heads, s_total, (Q, K, V))
+
+
+def qk_norm_rope_bwd_qkhalf_pair(dQ, dK, dV, img, txt, batch, heads, s_total, out_dtype):
+    """Backward of both streams in one launch; the argument tuples of qk_norm_rope_bwd_pair.  Returns (dqkv_img, dqkv_txt), ADDS to dwq / dwk."""
+    return _qk_half("mmdit_qk_norm_rope_bwd_qkhalf", [img, txt], batch, heads, s_total, (dQ, dK, dV), out_dtype)
+
+
+def _qkhalf_operands(Q, K, V, what):
+    """Checks of the qk_half_dim attention launches: contiguous bf16 Q, K (batch, heads, S, 32) and V (batch, heads, S, 64)."""
+    if Q.dim() != 4:
+        raise RuntimeError(f"{what}: Q is (batch, heads, S, {_lib.QKHALF_QK_DIM}), got {tuple(Q.shape)}")
+    batch, heads, S, _ = Q.shape
+    for t, hd in ((Q, _lib.QKHALF_QK_DIM), (K, _lib.QKHALF_QK_DIM), (V, _lib.QKHALF_V_DIM)):
+        if t.dtype != torch.bfloat16 or tuple(t.shape) != (batch, heads, S, hd):
+            raise RuntimeError(f"{what}: Q, K are bfloat16 (batch, heads, S, {_lib.QKHALF_QK_DIM}) and V is (batch, heads, S, {_lib.QKHALF_V_DIM}), got {t.dtype} {tuple(t.shape)}")
+        _c(t)
+    return batch, heads, S
+
+
+def attn_fwd_qkhalf(Q, K, V, n_img, scale, mode):
+    """qk_half_dim=True: joint softmax attention with 32-wide queries / keys and 64-wide values (mmdit_attn_fwd_qkhalf).  Returns Ox
+    (batch, n_img, heads * 64), Oc (batch, S - n_img, heads * 64) or None, lse (batch, heads, S)."""
+    batch, heads, S = _qkhalf_operands(Q, K, V, "attn_fwd_qkhalf")
+    if not 1 <= n_img <= S or mode not in (0, 1):
+        raise RuntimeError(f"attn_fwd_qkhalf: 1 <= n_img <= S = {S} and mode 0 | 1, got n_img={n_img}, mode={mode}")
+    D = heads * _lib.QKHALF_V_DIM
+    Ox = torch.empty((batch, n_img, D), dtype=torch.bfloat16, device=Q.device)
+    Oc = torch.empty((batch, S - n_img, D), dtype=torch.bfloat16, device=Q.device) if S > n_img else None
+    lse = torch.empty((batch, heads, S), dtype=torch.float32, device=Q.device)
+    check(_lib.lib().mmdit_attn_fwd_qkhalf(_p(Q), _p(K), _p(V), batch, heads, S, n_img, float(scale), mode, _p(Ox), _p(Oc), _p(lse), _s()), "mmdit_attn_fwd_qkhalf")
+    return Ox, Oc, lse
+
+
+def attn_bwd_qkhalf(Q, K, V, Ox, Oc, dOx, dOc, lse, n_img, scale, out_dtype):
+    """Backward of attn_fwd_qkhalf (mmdit_attn_bwd_qkhalf): dQ, dK (batch, heads, S, 32) and dV (batch, heads, S, 64) in out_dtype; dOc None = zeros."""
+    batch, heads, S = _qkhalf_operands(Q, K, V, "attn_bwd_qkhalf")
+    if not 1 <= n_img <= S or out_dtype not in (torch.bfloat16, torch.float32):
+        raise RuntimeError(f"attn_bwd_qkhalf: 1 <= n_img <= S = {S} and bfloat16 | float32 gradients, got n_img={n_img}, {out_dtype}")
+    D = heads * _lib.QKHALF_V_DIM
+    for t, rows, name in ((Ox, n_img, "Ox"), (dOx, n_img, "dOx"), (Oc, S - n_img, "Oc"), (dOc, S - n_img, "dOc")):
+        if t is None and (name == "dOc" or (name == "Oc" and n_img == S)):
+            continue
+        # (the engine hands the streams over as (batch * tokens, heads * 64) rows: the same memory)
+        if t is None or t.dtype != torch.bfloat16 or t.shape[-1] != D or t.numel() != batch * rows * D:
+            raise RuntimeError(f"attn_bwd_qkhalf: {name} is bfloat16 (batch, tokens, heads * {_lib.QKHALF_V_DIM}) = {(batch, rows, D)}, got "
+                               f"{None if t is None else (t.dtype, tuple(t.shape))}")
+    if lse.dtype != torch.float32 or tuple(lse.shape) != (batch, heads, S):
+        raise RuntimeError(f"attn_bwd_qkhalf: lse is fp32 (batch, heads, S) = {(batch, heads, S)}, got {lse.dtype} {tuple(lse.shape)}")
+    delta = torch.empty((batch, heads, S), dtype=torch.float32, device=Q.device)
+    dQ = torch.empty(Q.shape, dtype=out_dtype, device=Q.device)
+    dK = torch.empty(K.shape, dtype=out_dtype, device=Q.device)
+    dV = torch.empty(V.shape, dtype=out_dtype, device=Q.device)
+    check(_lib.lib().mmdit_attn_bwd_qkhalf(_p(Q), _p(K), _p(V), _p(_c(Ox)), _p(_c(Oc)), _p(_c(dOx)), _p(_c(dOc)), _p(_c(lse)), _p(delta), batch, heads, S, n_img,
+                                           float(scale), _p(dQ), _p(dK), _p(dV), _dt(dQ), _s()), "mmdit_attn_bwd_qkhalf")
+    return dQ, dK, dV
+
+
 def _merge_status(status, what):
     if status == _lib.ERR_SHAPE:
         raise RuntimeError(f"{what}: kv_merge_attn averages adjacent token pairs -- the tokens of each stream, its offset and the joint length must be even")
