@@ -20,6 +20,7 @@ HEADER_EXT_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_ext.h")   # op
 HEADER_HD128_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_hd128.h")   # the head-width-128 entry points, outside it as well
 HEADER_ROPE3_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_rope3.h")   # the RoPE2dV2 entry points, outside it as well
 HEADER_QKHALF_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_qkhalf.h")   # the qk_half_dim entry points, outside it as well
+HEADER_TEXTLOSS_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_textloss.h")   # the text_loss entry point, outside it as well
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_SILU, ACT_SWIGLU, ACT_SWIGLU_BWD = 0, 1, 2, 3
@@ -171,6 +172,12 @@ _QKHALF_SIGNATURES = {
 }
 QKHALF_QK_DIM, QKHALF_V_DIM = 32, 64                   # MMDIT_QKHALF_QK_DIM / MMDIT_QKHALF_V_DIM
 ATTN_QKHALF_KEY_TILE, ATTN_QKHALF_QUERY_TILE = 32, 128   # MMDIT_ATTN_QKHALF_KEY_TILE / MMDIT_ATTN_QKHALF_QUERY_TILE
+# entry point of include/mmdit_hip_textloss.h (text_loss=True: the masked text-reconstruction loss of the training step)
+_TEXTLOSS_SIGNATURES = {
+    "mmdit_text_loss": ([_vp, _i, _vp, _i, _vp, _i64, _i, _f, _vp, _i, _vp, _vp, _vp], _i),
+}
+TEXT_LOSS_ROWS_PER_WG, TEXT_LOSS_MAX_PARTIALS = 4, 256   # MMDIT_TEXT_LOSS_ROWS_PER_WG / MMDIT_TEXT_LOSS_MAX_PARTIALS
+TEXT_LOSS_LANE_COLS, TEXT_LOSS_WAVE_COLS = 8, 512        # MMDIT_TEXT_LOSS_LANE_COLS / MMDIT_TEXT_LOSS_WAVE_COLS
 HEAD_DIMS = (64, 128)                                  # head widths the attention and QK-norm / RoPE kernels are built for
 ADAMW_CHUNK = 65536   # MMDIT_ADAMW_CHUNK
 ABI_VERSION = 10      # MMDIT_ABI_VERSION of include/mmdit_hip.h this binding mirrors
@@ -216,6 +223,13 @@ def declared_qkhalf_symbols():
     return sorted(set(re.findall(r"\b(mmdit_[a-z0-9_]+)\s*\(", txt)) - {"mmdit_stream_t"})
 
 
+def declared_textloss_symbols():
+    """Entry points declared by include/mmdit_hip_textloss.h (parsed the same way)."""
+    with open(HEADER_TEXTLOSS_PATH) as f:
+        txt = f.read()
+    return sorted(set(re.findall(r"\b(mmdit_[a-z0-9_]+)\s*\(", txt)) - {"mmdit_stream_t"})
+
+
 def lib():
     """Load the HIP library (once).  Raises RuntimeError if it is not built."""
     global _lib
@@ -234,7 +248,7 @@ def lib():
             pass
         L = ctypes.CDLL(LIB_PATH)
         for name, (argtypes, restype) in (list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_HD128_SIGNATURES.items()) + list(_ROPE3_SIGNATURES.items())
-                                          + list(_QKHALF_SIGNATURES.items())):
+                                          + list(_QKHALF_SIGNATURES.items()) + list(_TEXTLOSS_SIGNATURES.items())):
             fn = getattr(L, name)  # AttributeError -> symbol missing: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

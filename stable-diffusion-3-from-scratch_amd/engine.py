@@ -688,10 +688,13 @@ def text_fwd(m, W, c):
     return C, cn1, cn2
 
 
-def model_fwd(m, W, x_t, t, c, c_pooled, rope, keep=True, C=None):
+def model_fwd(m, W, x_t, t, c, c_pooled, rope, keep=True, C=None, text_head=True):
     """W: packed weights (see models/diff_model.py).  x_t (B,Cin,H,W); t (B,) fp32;
     c (B,tokens,2304); c_pooled (B,class_dim).  Returns v (B,Cin,H,W) fp32 and the saved state.
-    C: the text tokens from text_fwd() when the caller already has them (inference only: nothing is saved for their backward)."""
+    C: the text tokens from text_fwd() when the caller already has them (inference only: nothing is saved for their backward).
+    text_loss=True models (W.Wtxt / W.btxt, diff_model.py:215-217, 344-346): every block is a full dual block and the saved state carries
+    sv.txt = out_text_proj(final text stream), (B*tokens, 2304) fp32 -- no norm in front of it; text_head=False (the sampler, which discards
+    the prediction) skips the head GEMM only: the last block still runs its text half."""
     B, Cin, Hh, Ww = x_t.shape
     d, H = W.dim, W.heads
     N, Mt = (Hh // 2) * (Ww // 2), c.shape[1]
@@ -719,6 +722,12 @@ def model_fwd(m, W, x_t, t, c, c_pooled, rope, keep=True, C=None):
     sv.Xf, sv.lnf, sv.muf, sv.rsf = _norm(m, X, sv.modo[:, d:], sv.modo[:, :d], N)
     Z = _gemm(m, sv.lnf, W.Wout, bias=W.bout, out_dtype=F32)
     v = ops.unpatchify(Z, B, Cin, Hh, Ww, F32)
+    sv.txt = None
+    if getattr(W, "Wtxt", None) is not None and text_head:
+        # the last block's text stream still carries its pending MLP update: no adaLN follows that would form it, so it is materialised here;
+        # a non-block GEMM like the output projection: bf16 in the fp8 / mxfp8 modes as well
+        sv.Cfa = m.act(C.value() if isinstance(C, Pending) else C)
+        sv.txt = _gemm(m, sv.Cfa, W.Wtxt, bias=W.btxt, out_dtype=F32)
     return v, sv
 
 
@@ -743,10 +752,12 @@ def _set_grad_tensors(g, new, pos=0):
     return pos
 
 
-def model_bwd(m, W, sv, dv, rope, on_grads=None):
+def model_bwd(m, W, sv, dv, rope, on_grads=None, dtxt=None):
     """Returns grads: NS with top-level packed-weight grads and .blocks = [block grads].
     on_grads(list_of_tensors) is called as soon as a group of parameter gradients is final (block by
-    block, last block first) so a data-parallel reducer can overlap its collective with the rest."""
+    block, last block first) so a data-parallel reducer can overlap its collective with the rest.
+    dtxt: gradient of sv.txt (text_loss=True models), (B*tokens, 2304); None = zeros (only v received a gradient: every parameter of the
+    text head and of the last block's text half still gets a gradient tensor, through the same launches)."""
     B, N, Mt, H, d = sv.dims
     _, Cin, Hh, Ww = sv.img
     dev = dv.device
@@ -780,6 +791,27 @@ def model_bwd(m, W, sv, dv, rope, on_grads=None):
     defer("Wmod_out", dmodo_a, sv.y)
 
     dC = None
+    if getattr(W, "Wtxt", None) is not None:
+        # text head: txt = C_final Wtxt^T + btxt with C_final = C1 + gate2c * acc_mc of the (full, dual) last block.  The text stream reaches the
+        # head through no adaLN, so no producer kernel carries the gated-residual backward of that MLP update: it is formed here, from the
+        # operands block_bwd_begin laid out (sts[-1].req_c), and handed to the block beside the image stream's
+        if sv.txt is None:
+            raise RuntimeError("model_bwd: the forward ran with text_head=False (nothing was saved for the text head's backward)")
+        rows_t = B * Mt
+        if dtxt is None:
+            dtxt_a = torch.zeros((rows_t, W.Wtxt.shape[0]), dtype=m.T, device=dev)
+        else:
+            dtxt = dtxt.reshape(rows_t, W.Wtxt.shape[0])
+            if not dtxt.is_contiguous():
+                dtxt = dtxt.contiguous()
+            dtxt_a = m.act(dtxt)
+        g.btxt = ops.zeros(W.Wtxt.shape[0], dev)
+        ops.colsum(dtxt_a if dtxt is None else dtxt, g.btxt)
+        dC = _dgrad(m, dtxt_a, W.Wtxt, F32)
+        defer("Wtxt", dtxt_a, sv.Cfa)
+        if _FUSE_GATE:
+            acc_mc, gate2c, dgate2c, bpart_c = sts[-1].req_c
+            dacc = (dacc[0], ops.gate_residual_bwd(dC, acc_mc, gate2c, Mt, dgate2c, bpart_c, m.T))
     g.blocks = [None] * nblk
     dmods = [None] * nblk
     yps = [None] * nblk

@@ -153,6 +153,26 @@ class _FlowLoss(torch.autograd.Function):
         return dv.mul_(g), None, None, None
 
 
+class _TextLoss(torch.autograd.Function):
+    """coef * sum over the masked tokens of sum_c (txt_pred - labels)^2 through ops.text_loss (reference model_trainer.py:450-454: with
+    coef = text_loss_weight / (numel * accumulation_steps) this is text_loss_weight * (MSE(txt_pred, labels) * mask[:, :, None]).mean() /
+    accumulation_steps): the forward also forms the gradient, the backward scales it by the incoming gradient (the GradScaler's loss scale)."""
+
+    @staticmethod
+    def forward(ctx, txt_pred, labels, mask, coef):
+        from . import ops
+        loss, ctx.d = ops.text_loss(txt_pred, labels, mask, coef, grad_dtype=torch.float32 if ctx.needs_input_grad[0] else None)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        d, ctx.d = ctx.d, None
+        return d.mul_(g), None, None, None
+
+
+TEXT_MASK_FRACTION = 0.25      # share of the text tokens drawn for the reconstruction loss (model_trainer.py:404)
+
+
 class model_trainer:
     def __init__(self, diff_model, batchSize, accumulation_steps, totalSteps, lr, ema_update_freq, ema_decay, warmup_steps, use_lr_scheduler,
                  device, saveDir, numSaveSteps, null_prob_pooled=0.1, null_prob_gemma=0.1, null_prob_bert=0.1, text_loss_weight=0.0,
@@ -174,8 +194,14 @@ class model_trainer:
         # (None: every step is issued from the host, as the reference does)
         self.graph_after = graph_after
         self.keep_graph = False      # True: capture_graph() keeps the hipGraph_t next to the executable graph (graph_node_types())
-        if text_loss_weight != 0.0:
-            raise RuntimeError("text_loss is out of scope on the HIP path (text_loss_weight must be 0)")
+        assert text_loss_weight >= 0.0
+        if text_loss_weight > 0.0 and not getattr(diff_model, "text_loss", False):
+            raise RuntimeError("text_loss_weight > 0 needs a model built with text_loss=True (the reference's train.py builds it with "
+                               "text_loss=(text_loss_weight > 0.0)): this model has no out_text_proj head")
+        # text_loss (model_trainer.py:399-454): a masked reconstruction term on the model's text prediction.  A text_loss model with weight 0
+        # trains on v alone (nothing extra is drawn: _draw() keeps its 7-tuple and the RNG streams of a run without the option)
+        self.text_loss_weight = float(text_loss_weight)
+        self.text_loss = self.text_loss_weight > 0.0
         if loader_to_model_gpu not in (None, {}):
             raise RuntimeError("loader GPUs are not used: every rank is a model rank; pass a data_source instead")
 
@@ -261,6 +287,12 @@ class model_trainer:
         self._gen = torch.Generator(device=self.device).manual_seed(4321 + self.rank) if device_rng else None
         self.inf_padded_latents = bool(inf_padded_latents)
         self.last_loss = None
+        # text_loss: the two terms of the last micro-step as the reference logs them (unweighted, before the division by accumulation_steps);
+        # device scalars in persistent buffers written by kernels of the step (no host synchronisation, valid under graph replay)
+        self.last_img_loss = self.last_text_loss = None
+        if self.text_loss:
+            self.last_img_loss = torch.zeros((), dtype=torch.float32, device=self.device)
+            self.last_text_loss = torch.zeros((), dtype=torch.float32, device=self.device)
         self._graph, self._slots, self._loss_out, self._graph_loss = None, None, None, None
         self._slots_primed = False   # the batches drawn at capture time are the inputs of the first replay (nothing drawn is dropped)
         self.replayed_steps = 0      # optimizer steps served by the hipGraph so far
@@ -286,17 +318,35 @@ class model_trainer:
         return t, mk(pp, self.null_prob_pooled), mk(pg, self.null_prob_gemma), mk(pb, self.null_prob_bert)
 
     def _draw(self):
-        """One micro-batch and its conditioning draw: (x0, text, pooled, t, null_pooled, null_gemma, null_bert)."""
+        """One micro-batch and its conditioning draw: (x0, text, pooled, t, null_pooled, null_gemma, null_bert).
+        text_loss_weight > 0: the token mask of the text loss is drawn after the null masks (model_trainer.py:399-414) and the tuple is
+        (x0, masked text, pooled, t, null_pooled, null_gemma, null_bert, labels, mask): mask (B, tokens) bool = rand < 0.25, ANDed with
+        null_gemma on the first 77 tokens and with null_bert on the others (the reference as written: loss on null-conditioned samples only);
+        masked text = text * ~mask; labels = the unmasked text (a tensor of its own: the model null-masks its input in place)."""
         with torch.no_grad():
             batch_x_0, batch_txt, batch_txt_pooled = self.data_source()
             if self.inf_padded_latents:      # latents arrive in the reference's +inf-padded wire format (model_trainer.py:362-370)
                 batch_x_0 = unpad_latents(batch_x_0)
-            return (batch_x_0, batch_txt, batch_txt_pooled) + tuple(self._sample_conditioning(batch_x_0.shape[0]))
+            cond = tuple(self._sample_conditioning(batch_x_0.shape[0]))
+            if not self.text_loss:
+                return (batch_x_0, batch_txt, batch_txt_pooled) + cond
+            n, tokens = batch_txt.shape[0], batch_txt.shape[1]
+            if self.device_rng:
+                mask = torch.rand((n, tokens), generator=self._gen, device=self.device) < TEXT_MASK_FRACTION
+            else:
+                mask = (torch.rand(n, tokens, dtype=torch.float) < TEXT_MASK_FRACTION).to(self.device)
+            n_gemma, n_bert = cond[2].to(mask.device), cond[3].to(mask.device)
+            mask = torch.cat([mask[:, :77] & n_gemma[:, None], mask[:, 77:] & n_bert[:, None]], dim=1)
+            labels = batch_txt.to(mask.device)
+            masked = labels * ~mask[:, :, None]
+            return (batch_x_0, masked, batch_txt_pooled) + cond + (labels, mask)
 
     def micro_step(self, final: bool, inputs=None):
         """One forward/backward micro-step; returns the (already /accumulation_steps) loss tensor.  inputs: a _draw() result (the graph
         path passes its static input slots), None: draw here."""
-        batch_x_0, batch_txt, batch_txt_pooled, t_vals, n_pooled, n_gemma, n_bert = inputs if inputs is not None else self._draw()
+        inputs = inputs if inputs is not None else self._draw()
+        batch_x_0, batch_txt, batch_txt_pooled, t_vals, n_pooled, n_gemma, n_bert = inputs[:7]
+        txt_labels, txt_mask = inputs[7:] if self.text_loss else (None, None)
         with torch.no_grad():
             batch_x_t, epsilon_t = self.model.noise_batch(batch_x_0, t_vals)
         # Gradient accumulation = DDP.no_sync (reference model_trainer.py:463-480): nothing is reduced on non-final micro-steps.
@@ -310,6 +360,9 @@ class model_trainer:
         late = engine_path and self.accumulation_steps > 1
         self.reducer.skip = (not final) or late
         v_pred = self.model(batch_x_t.detach(), t_vals, batch_txt, batch_txt_pooled, n_pooled, n_gemma, n_bert)
+        txt_pred = None
+        if getattr(self.model, "text_loss", False):      # (v, txt_pred); with weight 0 the prediction is dropped and its gradient is zeros
+            v_pred, txt_pred = v_pred
         x0 = batch_x_0.to(epsilon_t.device)
         if self.hip_loss and v_pred.is_cuda and v_pred.dtype == torch.float32 and x0.dtype == epsilon_t.dtype and v_pred.numel() % 8 == 0:
             # same arithmetic as the torch expression below in two HIP launches with a bit-reproducible reduction (ops.flow_loss)
@@ -318,6 +371,17 @@ class model_trainer:
             labels = epsilon_t - x0
             loss = nn.MSELoss(reduction="none")(v_pred, labels.detach().to(v_pred.dtype)).flatten(1, -1).mean()
             loss = loss / self.accumulation_steps
+        if self.text_loss:
+            # loss = (img + text_loss_weight * txt) / accumulation_steps (model_trainer.py:450-463) with txt = (MSE * mask[:, :, None]).mean()
+            w, acc = self.text_loss_weight, self.accumulation_steps
+            if self.hip_loss and txt_pred.is_cuda and txt_pred.shape[-1] % 8 == 0 and txt_labels.dtype in (torch.float32, torch.bfloat16):
+                # the masked term as two HIP launches that read the masked rows only (ops.text_loss), bit-reproducible like the flow loss
+                term = _TextLoss.apply(txt_pred, txt_labels.contiguous(), txt_mask.contiguous(), w / (txt_pred.numel() * acc))
+            else:
+                term = (nn.MSELoss(reduction="none")(txt_pred, txt_labels.detach().to(txt_pred.dtype)) * txt_mask[:, :, None]).mean() * (w / acc)
+            torch.mul(loss.detach(), float(acc), out=self.last_img_loss)
+            torch.mul(term.detach(), acc / w, out=self.last_text_loss)
+            loss = loss + term
         if self.grad_scaler is not None:
             self.grad_scaler.scale(loss).backward()
         else:

@@ -7,7 +7,9 @@ JSON always records device "cpu", attn_type string preserved).  positional_encod
 configuration) or "RoPE2dV2" (blocks/rotary_embedding_2d_v2.py: `rotary_emb.inv_freq` buffers in place of the `rotary_emb.freqs`
 parameters; "fast" / "parity" precision, no kv_merge_attn); the other three values of the reference raise.  qk_half_dim=True (queries and
 keys projected to dim / 2: 32-wide query / key heads, 64-wide values; include/mmdit_hip_qkhalf.h) is built for dim = 64 * num_heads with
-"RoPE2d" at "fast" / "parity" precision; with kv_merge_attn, "RoPE2dV2", dim = 128 * num_heads or fp8 / mxfp8 it raises.  The arithmetic of forward() and of
+"RoPE2d" at "fast" / "parity" precision; with kv_merge_attn, "RoPE2dV2", dim = 128 * num_heads or fp8 / mxfp8 it raises.  text_loss=True (every
+block a full dual block, `out_text_proj` on the final text stream, forward returns (v, txt_pred); include/mmdit_hip_textloss.h is the trainer's
+masked loss) composes with every option above except kv_merge_attn, with which it raises.  The arithmetic of forward() and of
 its backward runs in libmmdit_hip.so through sd3_amd.engine; there is no PyTorch/CPU fallback.
 """
 import json
@@ -38,11 +40,16 @@ class _MMDiTFn(torch.autograd.Function):
         v, sv = engine.model_fwd(m, W, x_t, t, c, c_pooled, rope, keep=net._keep_saved)
         if any(ctx.needs_input_grad):
             ctx.net, ctx.m, ctx.sv, ctx.rope = net, m, sv, rope
+        if net.text_loss:      # (v, txt_pred): the prediction of the text embedding from the final text stream, fp32 (B, tokens, 2304)
+            ctx.set_materialize_grads(False)      # an output without a gradient arrives as None in backward (engine.model_bwd: dtxt=None)
+            return v, sv.txt.view(c.shape[0], c.shape[1], sv.txt.shape[1])
         return v
 
     @staticmethod
-    def backward(ctx, dv):
+    def backward(ctx, dv, dtxt=None):
         net, m = ctx.net, ctx.m
+        if dv is None:      # (only txt_pred received a gradient)
+            dv = torch.zeros(ctx.sv.img, dtype=torch.float32, device=ctx.sv.t.device)
         W = net.weights(m)
         red = net.grad_reducer
         # Data parallel: the collectives of the reducer's side stream run beside THIS pass and hold compute units the GEMMs cannot share.  The weight-gradient
@@ -53,7 +60,7 @@ class _MMDiTFn(torch.autograd.Function):
         budget = getattr(net, "bwd_cu_budget", None)
         before, ops.WGRAD_CU_BUDGET = ops.WGRAD_CU_BUDGET, (int(budget) if budget else None)
         try:
-            g = engine.model_bwd(m, W, ctx.sv, dv, ctx.rope, on_grads=red.add_bucket if red is not None else None)
+            g = engine.model_bwd(m, W, ctx.sv, dv, ctx.rope, on_grads=red.add_bucket if red is not None else None, dtxt=dtxt)
         finally:
             ops.WGRAD_CU_BUDGET = before
         ctx.sv = None
@@ -66,7 +73,8 @@ class diff_model(nn.Module):
     # inCh - number of latent channels; class_dim - pooled text embedding width; patch_size - 2;
     # dim / hidden_scale / num_heads / num_blocks - transformer geometry (dim = 64*num_heads, or 128*num_heads);
     # attn_type - "softmax" | "softmax_flash"; MLP_type - "swiglu" | "gelu"; positional_encoding - "RoPE2d" | "RoPE2dV2";
-    # qk_half_dim - queries / keys projected to dim / 2 (dim = 64*num_heads, "RoPE2d", no kv_merge_attn)
+    # qk_half_dim - queries / keys projected to dim / 2 (dim = 64*num_heads, "RoPE2d", no kv_merge_attn);
+    # text_loss - full last block + out_text_proj head, forward returns (v, txt_pred) (no kv_merge_attn)
     def __init__(self, inCh, class_dim, patch_size, dim, hidden_scale, num_heads, attn_type, MLP_type, num_blocks, device, positional_encoding,
                  max_res_orig=256, max_res=256, update_max_res=False, kv_merge_attn=False, qk_half_dim=False, text_loss=False,
                  checkpoint_MLP=True, checkpoint_attn=True, start_step=0, wandb_id=None):
@@ -79,10 +87,13 @@ class diff_model(nn.Module):
 
         assert positional_encoding in ["absolute", "RoPE", "NoPE", "RoPE2d", "RoPE2dV2"], "positional_encoding must be 'absolute', 'RoPE', or 'NoPE' or 'RoPE2d' or 'RoPE2dV2'"
         assert MLP_type in ["gelu", "swiglu", "swiglu_old"]
-        if positional_encoding not in ("RoPE2d", "RoPE2dV2") or text_loss or MLP_type == "swiglu_old":
+        if positional_encoding not in ("RoPE2d", "RoPE2dV2") or MLP_type == "swiglu_old":
             raise RuntimeError("diff_model (HIP path): only the trained configuration is implemented: positional_encoding='RoPE2d' (or 'RoPE2dV2'), "
-                               "MLP_type in {'swiglu','gelu'}, text_loss=False")
+                               "MLP_type in {'swiglu','gelu'}")
         self.kv_merge_attn = bool(kv_merge_attn)
+        if text_loss and self.kv_merge_attn:
+            raise RuntimeError("diff_model (HIP path): text_loss is not built with kv_merge_attn (the last block of a text_loss model attends for its "
+                               "text queries too, a form the pair-averaged path was never run in); use one of the two options")
         self.qk_half_dim = bool(qk_half_dim)
         self.positional_encoding = positional_encoding
         if self.qk_half_dim and self.kv_merge_attn:
@@ -154,6 +165,8 @@ class diff_model(nn.Module):
         self.out_norm = Norm(dim, dim).to(device)
         self.out_proj = nn.Linear(dim, inCh * patch_size * patch_size).to(device)
         self.time_scale = nn.Parameter(torch.tensor([1000.0], dtype=torch.float, device=device), requires_grad=True)
+        if self.text_loss:      # (registered after time_scale: diff_model.py:215-217)
+            self.out_text_proj = nn.Linear(dim, self.text_hidden_shape).to(device)
 
         # "fast" = bf16 MFMA operands (training default, = the reference's bf16 autocast);
         # "parity" = split-bf16 GEMMs + reference-rounding attention for the 1e-3 golden check.
@@ -164,6 +177,8 @@ class diff_model(nn.Module):
         self._packs = NS(Wt=Pack([self.t_emb2.weight]), Wcond=Pack([self.cond_MLP.weight]), Wc1=Pack([self.c_proj.weight]),
                          Wc2=Pack([self.c_proj2.weight]), Wpatch=Pack([self.pos_enc.proj.weight]), Wpe=Pack([self.patch_emb.weight]),
                          Wmod_out=Pack([self.out_norm.c_shift.weight, self.out_norm.c_scale.weight]), Wout=Pack([self.out_proj.weight]))
+        if self.text_loss:
+            self._packs.Wtxt = Pack([self.out_text_proj.weight])
 
     # ------------------------------------------------------------------------------------------
     @staticmethod
@@ -218,6 +233,7 @@ class diff_model(nn.Module):
                   s1=self.learnable_scalar.detach(), s2=self.learnable_scalar2.detach(),
                   Wpatch=P.Wpatch.get(m), Wpe=P.Wpe.get(m), bpe=self.patch_emb.bias.detach(),
                   Wmod_out=P.Wmod_out.get(m), Wout=P.Wout.get(m), bout=self.out_proj.bias.detach(),
+                  Wtxt=P.Wtxt.get(m) if self.text_loss else None, btxt=self.out_text_proj.bias.detach() if self.text_loss else None,
                   blocks=[b.weights(m) for b in self.blocks])
 
     def scatter_grads(self, g, out: dict):
@@ -228,6 +244,9 @@ class diff_model(nn.Module):
         out[id(self.learnable_scalar)], out[id(self.learnable_scalar2)] = g.s1, g.s2
         out[id(self.patch_emb.bias)], out[id(self.out_proj.bias)] = g.bpe, g.bout
         out[id(self.time_scale)] = g.time_scale
+        if self.text_loss:
+            P.Wtxt.split_grad(g.Wtxt, out)
+            out[id(self.out_text_proj.bias)] = g.btxt
         for b, gb in zip(self.blocks, g.blocks):
             b.scatter_grads(gb, out)
 
@@ -330,7 +349,7 @@ class diff_model(nn.Module):
 
         def velocity(t_now):
             tt.fill_(t_now)
-            v = engine.model_fwd(m, W, xx, tt, c, cp, rope, keep=False, C=C_text)[0]
+            v = engine.model_fwd(m, W, xx, tt, c, cp, rope, keep=False, C=C_text, text_head=False)[0]      # (text_loss: the head's output is discarded here)
             return (1 + cfg_scale) * v[:B] - cfg_scale * v[B:]
 
         def decode(z):

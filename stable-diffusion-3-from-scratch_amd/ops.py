@@ -1038,6 +1038,37 @@ def flow_loss(v, x0, eps, accumulation_steps=1, need_grad=True):
     return loss, dv
 
 
+def text_loss(pred, label, mask, coef, grad_dtype=None):
+    """Masked text-reconstruction loss coef * sum over rows with mask[r] of sum_c (pred - label)^2 (mmdit_text_loss, include/mmdit_hip_textloss.h):
+    returns (loss 0-dim fp32, dpred = d loss / d pred in grad_dtype, or None when grad_dtype is None).  pred / label: (..., cols) contiguous, bf16 or
+    fp32 each, the same shape; mask: torch.bool, one entry per row (pred.shape[:-1]).  Rows the mask excludes are never read; dpred is +0 there."""
+    if pred.dim() < 2 or label.shape != pred.shape:
+        raise RuntimeError(f"text_loss: pred and label must have one shape (..., cols), got {tuple(pred.shape)} and {tuple(label.shape)}")
+    cols = pred.shape[-1]
+    rows = pred.numel() // max(cols, 1)
+    if mask.dtype != torch.bool or mask.numel() != rows or tuple(mask.shape) != tuple(pred.shape[:-1]):
+        raise RuntimeError(f"text_loss: mask must be a torch.bool tensor of shape {tuple(pred.shape[:-1])} (one entry per row), got {mask.dtype} {tuple(mask.shape)}")
+    if rows < 1 or cols < 8 or cols % 8:
+        raise RuntimeError(f"text_loss: needs at least one row and cols % 8 == 0 (16-byte loads), got rows={rows}, cols={cols}")
+    for t, what in ((pred, "pred"), (label, "label")):
+        if t.dtype not in (torch.float32, torch.bfloat16):
+            raise RuntimeError(f"text_loss: {what} must be float32 or bfloat16, got {t.dtype}")
+    if grad_dtype not in (None, torch.float32, torch.bfloat16):
+        raise RuntimeError(f"text_loss: grad_dtype must be None, float32 or bfloat16, got {grad_dtype}")
+    if pred.device != label.device or pred.device != mask.device:
+        raise RuntimeError("text_loss: pred, label and mask must live on one device")
+    pred, label, mask = _c(pred), _c(label), _c(mask)
+    if pred.data_ptr() % 16 or label.data_ptr() % 16:
+        raise RuntimeError("text_loss: pred and label must be 16-byte aligned")
+    _p(pred), _p(label), _p(mask)      # (a CPU tensor raises here, before anything is allocated)
+    loss = torch.empty((), dtype=torch.float32, device=pred.device)
+    part = torch.empty(_lib.TEXT_LOSS_MAX_PARTIALS, dtype=torch.float32, device=pred.device)
+    dpred = torch.empty(pred.shape, dtype=grad_dtype, device=pred.device) if grad_dtype is not None else None
+    check(_lib.lib().mmdit_text_loss(_p(pred), _dt(pred), _p(label), _dt(label), _p(mask), rows, cols, float(coef), _p(dpred), _dt(dpred) if dpred is not None else F32,
+                                     _p(part), _p(loss), _s()), "mmdit_text_loss")
+    return loss, dpred
+
+
 def colsum(x, out):
     rows, cols = x.shape
     check(_lib.lib().mmdit_colsum(_p(x), _dt(x), rows, cols, x.stride(0), _p(out), _s()), "mmdit_colsum")

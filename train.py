@@ -40,6 +40,7 @@ def main():
     ap.add_argument("--log-steps", type=int, default=10)
     ap.add_argument("--load", nargs=2, metavar=("DIR", "STEP"), help="resume: loadModel(DIR, model_<STEP>s.pkl, model_params_<STEP>s.json) + optimizer / scheduler / scaler / EMA files")
     ap.add_argument("--vae-in-rank", action="store_true", help="synthetic images -> HIP FLUX-VAE encode inside the rank (SURVEY 8f-1)")
+    ap.add_argument("--text-loss-weight", type=float, default=0.0, help="weight of the masked text-reconstruction loss (src/train.py:66); > 0 builds the model with text_loss=True")
     ap.add_argument("--json", action="store_true", help="print one summary JSON line at the end (tests)")
     a = ap.parse_args()
 
@@ -76,7 +77,7 @@ def main():
     model = diff_model(inCh=inCh, class_dim=class_dim, patch_size=patch_size, dim=dim, hidden_scale=hidden_scale, num_heads=num_heads,
                        attn_type=attn_type, MLP_type=MLP_type, num_blocks=num_blocks, checkpoint_MLP=checkpoint_MLP, checkpoint_attn=checkpoint_attn,
                        positional_encoding=positional_encoding, max_res_orig=max_res_orig, max_res=max_res, update_max_res=True,
-                       kv_merge_attn=False, qk_half_dim=False, text_loss=False, device=device)
+                       kv_merge_attn=False, qk_half_dim=False, text_loss=(a.text_loss_weight > 0.0), device=device)
     files = {}
     if a.load:
         d, s = a.load
@@ -93,7 +94,7 @@ def main():
     trainer = model_trainer(diff_model=model, batchSize=a.batch, accumulation_steps=a.accumulation_steps, totalSteps=a.steps, lr=lr,
                             ema_update_freq=ema_update_freq, ema_decay=ema_decay, warmup_steps=warmup_steps, use_lr_scheduler=use_lr_scheduler,
                             saveDir=a.save_dir, numSaveSteps=a.save_steps, null_prob_pooled=null_prob_pooled, null_prob_gemma=null_prob_gemma,
-                            null_prob_bert=null_prob_bert, text_loss_weight=0.0, use_amp=True, log_steps=1 if json_log else a.log_steps,
+                            null_prob_bert=null_prob_bert, text_loss_weight=a.text_loss_weight, use_amp=True, log_steps=1 if json_log else a.log_steps,
                             device=device, max_res=max_res, data_source=data_source, device_rng=True, graph_after=a.graph_after,
                             log_file=None, **files)
     trainer.keep_losses = a.json
