@@ -21,6 +21,7 @@ HEADER_HD128_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_hd128.h")   
 HEADER_ROPE3_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_rope3.h")   # the RoPE2dV2 entry points, outside it as well
 HEADER_QKHALF_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_qkhalf.h")   # the qk_half_dim entry points, outside it as well
 HEADER_TEXTLOSS_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_textloss.h")   # the text_loss entry point, outside it as well
+HEADER_COS2_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_cos2.h")   # the attn_type="cosine2" entry points, outside it as well
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_SILU, ACT_SWIGLU, ACT_SWIGLU_BWD = 0, 1, 2, 3
@@ -178,6 +179,16 @@ _TEXTLOSS_SIGNATURES = {
 }
 TEXT_LOSS_ROWS_PER_WG, TEXT_LOSS_MAX_PARTIALS = 4, 256   # MMDIT_TEXT_LOSS_ROWS_PER_WG / MMDIT_TEXT_LOSS_MAX_PARTIALS
 TEXT_LOSS_LANE_COLS, TEXT_LOSS_WAVE_COLS = 8, 512        # MMDIT_TEXT_LOSS_LANE_COLS / MMDIT_TEXT_LOSS_WAVE_COLS
+# entry points of include/mmdit_hip_cos2.h (attn_type="cosine2": L2-normalised queries / keys, linear-time attention through a 64 x 64 state)
+_COS2_SIGNATURES = {
+    "mmdit_qk_l2norm_rope_fwd": ([ctypes.POINTER(QkProblem), _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "mmdit_qk_l2norm_rope_bwd": ([ctypes.POINTER(QkProblem), _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
+    "mmdit_attn_cos2_ws_bytes": ([_i, _i, _i], ctypes.c_longlong),
+    "mmdit_attn_cos2_fwd": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp], _i),
+    "mmdit_attn_cos2_bwd": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp], _i),
+}
+COS2_HEAD_DIM = 64                                     # MMDIT_COS2_HEAD_DIM
+ATTN_COS2_TOKEN_CHUNK, ATTN_COS2_ROW_TILE = 128, 64    # MMDIT_ATTN_COS2_TOKEN_CHUNK / MMDIT_ATTN_COS2_ROW_TILE
 HEAD_DIMS = (64, 128)                                  # head widths the attention and QK-norm / RoPE kernels are built for
 ADAMW_CHUNK = 65536   # MMDIT_ADAMW_CHUNK
 ABI_VERSION = 10      # MMDIT_ABI_VERSION of include/mmdit_hip.h this binding mirrors
@@ -230,6 +241,13 @@ def declared_textloss_symbols():
     return sorted(set(re.findall(r"\b(mmdit_[a-z0-9_]+)\s*\(", txt)) - {"mmdit_stream_t"})
 
 
+def declared_cos2_symbols():
+    """Entry points declared by include/mmdit_hip_cos2.h (parsed the same way)."""
+    with open(HEADER_COS2_PATH) as f:
+        txt = f.read()
+    return sorted(set(re.findall(r"\b(mmdit_[a-z0-9_]+)\s*\(", txt)) - {"mmdit_stream_t"})
+
+
 def lib():
     """Load the HIP library (once).  Raises RuntimeError if it is not built."""
     global _lib
@@ -248,7 +266,7 @@ def lib():
             pass
         L = ctypes.CDLL(LIB_PATH)
         for name, (argtypes, restype) in (list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_HD128_SIGNATURES.items()) + list(_ROPE3_SIGNATURES.items())
-                                          + list(_QKHALF_SIGNATURES.items()) + list(_TEXTLOSS_SIGNATURES.items())):
+                                          + list(_QKHALF_SIGNATURES.items()) + list(_TEXTLOSS_SIGNATURES.items()) + list(_COS2_SIGNATURES.items())):
             fn = getattr(L, name)  # AttributeError -> symbol missing: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

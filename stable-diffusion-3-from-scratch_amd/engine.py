@@ -339,6 +339,13 @@ def block_fwd(m, w, X, C, y, dims, rope, cond=None, keep=True, lazy=False):
         raise RuntimeError("qk_half_dim: no fp8 / mxfp8 path")      # (direct engine use; diff_model.set_precision refuses it first)
     if qk_half and (w.kv_merge or w.rope3 or w.hd != 64):
         raise RuntimeError("qk_half_dim: built for RoPE2d at head width 64 without kv_merge_attn only")      # (direct engine use; Attention refuses it at construction)
+    # attn_type="cosine2" (hand-built weight namespaces of other callers lack the flag): L2-normalised queries / keys, no norm weights, linear-time
+    # attention (ops.attn_cos2_*) -- the unfused route, "fast" / "parity" only, Q / K / V / O in the activation dtype
+    cos2 = getattr(w, "cos2", False)
+    if cos2 and m.fp8:
+        raise RuntimeError("cosine2: no fp8 / mxfp8 path")      # (direct engine use; diff_model.set_precision refuses it first)
+    if cos2 and (w.kv_merge or w.rope3 or qk_half or w.hd != 64):
+        raise RuntimeError("cosine2: built for RoPE2d at head width 64 without kv_merge_attn and qk_half_dim only")      # (direct engine use; Attention refuses it at construction)
     sv = NS(y=y)
     if cond is not None:
         sv.pre, sv.yp, sv.mod = cond
@@ -356,7 +363,7 @@ def block_fwd(m, w, X, C, y, dims, rope, cond=None, keep=True, lazy=False):
     hd = w.hd      # head width: 64, or 128 (the unfused route below: no QKV epilogue, no fused QK backward, no e4m3 / MX forms)
     if hd != 64 and m.fp8:
         raise RuntimeError(f"head width {hd}: no fp8 / mxfp8 path (the e4m3 GEMM epilogues and attention kernels are built for head width 64)")      # (direct engine use; diff_model.set_precision refuses it first)
-    sv.Q = torch.empty((B, H, S, hd // 2 if qk_half else hd), dtype=BF16, device=dev)
+    sv.Q = torch.empty((B, H, S, hd // 2 if qk_half else hd), dtype=m.T if cos2 else BF16, device=dev)
     # kv_merge_attn (Attention.py:243-251): the keys / values of adjacent token pairs are averaged -- K / V have S / 2 rows.  A GEMM epilogue sees
     # one token per row, so the plain grouped QKV GEMM and the merging norm / RoPE kernel run instead of the fused launch
     merge = w.kv_merge
@@ -371,9 +378,9 @@ def block_fwd(m, w, X, C, y, dims, rope, cond=None, keep=True, lazy=False):
             raise RuntimeError(f"kv_merge_attn: head width {hd} is not built (the pair-averaging kernels are 64 wide)")      # (direct engine use; Attention refuses it at construction)
         sv.K, sv.V = torch.empty((B, H, S // 2, 64), dtype=BF16, device=dev), torch.empty((B, H, S // 2, 64), dtype=BF16, device=dev)
     else:
-        sv.K, sv.V = torch.empty_like(sv.Q), torch.empty((B, H, S, hd), dtype=BF16, device=dev)
+        sv.K, sv.V = torch.empty_like(sv.Q), torch.empty((B, H, S, hd), dtype=sv.Q.dtype, device=dev)
     fused = None
-    if not merge and not rope3 and not qk_half and _QKV_FUSE and m.fast and dev.type == "cuda" and m.T == BF16 and (not m.fp8 or mxf) and hd == 64:
+    if not merge and not rope3 and not qk_half and not cos2 and _QKV_FUSE and m.fast and dev.type == "cuda" and m.T == BF16 and (not m.fp8 or mxf) and hd == 64:
         # QK-norm + RoPE + joint-layout store in the QKV GEMM's epilogue (one launch, no second pass over the raw projection); None: the
         # planner would not give these problems to a kernel with that epilogue (bf16: the lean wide-slot kernel; MX operands: the 8-phase kernel)
         qp = [dict(A=sv.ln1x, B=w.Wqkv_x, out_dtype=m.T, precision=m.prec), dict(A=sv.ln1c, B=w.Wqkv_c, out_dtype=m.T, precision=m.prec)]
@@ -389,6 +396,8 @@ def block_fwd(m, w, X, C, y, dims, rope, cond=None, keep=True, lazy=False):
         sv.qkv_x, sv.qkv_c = _group(m, [dict(A=sv.ln1x, B=w.Wqkv_x, out_dtype=m.T), dict(A=sv.ln1c, B=w.Wqkv_c, out_dtype=m.T)], fp8=True)
     if fused is not None:
         pass
+    elif cos2:
+        ops.qk_l2norm_rope_fwd_pair((sv.qkv_x, rope[0], rope[1], N, 0), (sv.qkv_c, None, None, Mt, N), B, H, S, sv.Q, sv.K, sv.V)
     elif qk_half:      # rows [q H*32 | k H*32 | v H*64] of the N = 2 d projection
         ops.qk_norm_rope_fwd_qkhalf_pair((sv.qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], N, 0), (sv.qkv_c, w.wq_c, w.wk_c, None, None, Mt, N), B, H, S, sv.Q, sv.K, sv.V)
     elif rope3:
@@ -400,7 +409,12 @@ def block_fwd(m, w, X, C, y, dims, rope, cond=None, keep=True, lazy=False):
     else:
         ops.qk_norm_rope_fwd(sv.qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], B, N, H, S, 0, sv.Q, sv.K, sv.V)
         ops.qk_norm_rope_fwd(sv.qkv_c, w.wq_c, w.wk_c, None, None, B, Mt, H, S, N, sv.Q, sv.K, sv.V)
-    if qk_half:      # (scale from the VALUE width, Attention.py:57)
+    if cos2:      # (no scale; den takes lse's place in the saved state)
+        sv.Ox, sv.Oc, sv.den = ops.attn_cos2_fwd(sv.Q, sv.K, sv.V, N)
+        sv.Oxa = sv.Ox.view(B * N, d)
+        if both:
+            sv.Oca = sv.Oc.view(B * Mt, d)
+    elif qk_half:      # (scale from the VALUE width, Attention.py:57)
         sv.Ox, sv.Oc, sv.lse = ops.attn_fwd_qkhalf(sv.Q, sv.K, sv.V, N, hd ** -0.5, m.attn_mode)
         sv.Oxa = m.act(sv.Ox.view(B * N, d))
         if both:
@@ -490,6 +504,9 @@ def _qk_bwd_two_pass(m, w, sv, g, dOx, dOc, dims, rope, dev):
     """Attention backward, then the QK-norm + RoPE backward as a pass of its own."""
     B, N, Mt, H, d = dims
     S = N + Mt
+    if getattr(w, "cos2", False):
+        dQ, dK, dV = ops.attn_cos2_bwd(sv.Q, sv.K, sv.V, sv.Ox, sv.Oc, dOx, dOc, sv.den, N, m.T)
+        return ops.qk_l2norm_rope_bwd_pair(dQ, dK, dV, (sv.qkv_x, rope[0], rope[1], N, 0), (sv.qkv_c, None, None, Mt, N), B, H, S, m.T)
     if getattr(w, "qk_half", False):
         dQ, dK, dV = ops.attn_bwd_qkhalf(sv.Q, sv.K, sv.V, sv.Ox, sv.Oc, dOx, dOc, sv.lse, N, w.hd ** -0.5, m.T)
         return ops.qk_norm_rope_bwd_qkhalf_pair(dQ, dK, dV, (sv.qkv_x, w.wq_x, w.wk_x, rope[0], rope[1], N, 0, g.wq_x, g.wk_x),
@@ -524,18 +541,21 @@ def block_bwd_begin(m, w, sv, dims, dev, defer_cond=False):
     nb = 2 if both else 1
     # parameter gradients first (they form one flat sub-arena a reducer can average in place), scratch after them
     nw = w.hd // 2 if getattr(w, "qk_half", False) else w.hd      # (length of a QK-norm weight)
-    shapes = [(nb * d,), (hx,), (nw,), (nw,), (nw,), (nw,)] + ([(sv.gu_c.shape[1],)] if both else []) + ([] if defer_cond else [(d,)])
+    cos2 = getattr(w, "cos2", False)      # (no QK-norm weights: no slots for their gradients)
+    shapes = [(nb * d,), (hx,)] + ([] if cos2 else [(nw,), (nw,), (nw,), (nw,)]) + ([(sv.gu_c.shape[1],)] if both else []) + ([] if defer_cond else [(d,)])
     npar = len(shapes)
     shapes += [tuple(sv.mod.shape), (B, nb * d)]
     zs, small_arena = _zeros_views(shapes, dev, prefix=npar)
     st = NS(g=g, ms=ms, zs=zs, npar=npar, small_arena=small_arena, both=both)
-    st.bdown, g.mlp_x.bup, g.wq_x, g.wk_x, g.wq_c, g.wk_c = zs[:6]
+    st.bdown, g.mlp_x.bup = zs[:2]
+    if not cos2:
+        g.wq_x, g.wk_x, g.wq_c, g.wk_c = zs[2:6]
     if not defer_cond:
         g.by = zs[npar - 1]
     st.dmod, st.bpart = zs[npar], zs[npar + 1]   # bpart: per-batch partial rows of the down-proj bias grads
     g.mlp_x.bdown = st.bdown[:d]
     if both:
-        g.mlp_c.bdown, g.mlp_c.bup = st.bdown[d:], zs[6]
+        g.mlp_c.bdown, g.mlp_c.bup = st.bdown[d:], zs[2 if cos2 else 6]
     st.dms = _mod_views(st.dmod, d, w.last)
     st.req_x = (sv.acc_mx, ms.gate2x, st.dms.gate2x, st.bpart[:, :d])
     st.req_c = (sv.acc_mc, ms.gate2c, st.dms.gate2c, st.bpart[:, d:]) if both else None
@@ -614,7 +634,8 @@ def block_bwd(m, w, sv, dX2, dC2, dy_acc, dims, rope, defer_cond=False, st=None,
     else:
         dX1 = rx
         dacc_x = ops.gate_residual_bwd(dX1, sv.acc_ox, ms.gate1x, N, dms.gate1x, None, m.T)
-    probs = [dict(A=dacc_x, B=w.Wo_x, b_kmajor=True, out_dtype=BF16)]
+    oT = m.T if getattr(w, "cos2", False) else BF16      # (dtype of the attention output's gradient: the softmax kernels take bf16)
+    probs = [dict(A=dacc_x, B=w.Wo_x, b_kmajor=True, out_dtype=oT)]
     defer(g, "Wo_x", dacc_x, sv.Oxa)
     if both:
         if fuse:
@@ -622,7 +643,7 @@ def block_bwd(m, w, sv, dX2, dC2, dy_acc, dims, rope, defer_cond=False, st=None,
         else:
             dC1 = rc
             dacc_c = ops.gate_residual_bwd(dC1, sv.acc_oc, ms.gate1c, Mt, dms.gate1c, None, m.T)
-        probs.append(dict(A=dacc_c, B=w.Wo_c, b_kmajor=True, out_dtype=BF16))
+        probs.append(dict(A=dacc_c, B=w.Wo_c, b_kmajor=True, out_dtype=oT))
         defer(g, "Wo_c", dacc_c, sv.Oca)
     dO = _group(m, probs)
     dOx, dOc = dO[0], (dO[1] if both else None)   # the last block's text attention output is discarded (Attention.py:425)
@@ -630,7 +651,7 @@ def block_bwd(m, w, sv, dX2, dC2, dy_acc, dims, rope, defer_cond=False, st=None,
     # ---- attention core + QK norm / RoPE
     # the QK-norm + RoPE backward runs in the epilogues of the attention backward kernels (ops.attn_bwd_qk) when the shapes allow it:
     # no dQ / dK / dV round trip, one pass less (MMDIT_ATTN_QK_FUSE=0: the two-pass form).  Head width 64 only (attn_bwd_qk_ok): the literals below are its
-    if not w.kv_merge and not w.rope3 and not getattr(w, "qk_half", False) and _QK_FUSE and m.fast and dev.type == "cuda" and ops.attn_bwd_qk_ok(sv.Q, N, sv.qkv_x) and g.wq_x.data_ptr() + 768 == g.wk_c.data_ptr():
+    if not w.kv_merge and not w.rope3 and not getattr(w, "qk_half", False) and not getattr(w, "cos2", False) and _QK_FUSE and m.fast and dev.type == "cuda" and ops.attn_bwd_qk_ok(sv.Q, N, sv.qkv_x) and g.wq_x.data_ptr() + 768 == g.wk_c.data_ptr():
         dqkv_x, dqkv_c = ops.attn_bwd_qk(sv.Q, sv.K, sv.V, sv.Ox, sv.Oc, dOx, dOc, sv.lse, N, 64 ** -0.5, sv.qkv_x, sv.qkv_c, w.wq_x, w.wk_x, w.wq_c, w.wk_c,
                                          rope[0], rope[1], torch.as_strided(g.wq_x, (256,), (1,)))
     else:

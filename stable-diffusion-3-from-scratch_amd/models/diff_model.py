@@ -9,7 +9,10 @@ parameters; "fast" / "parity" precision, no kv_merge_attn); the other three valu
 keys projected to dim / 2: 32-wide query / key heads, 64-wide values; include/mmdit_hip_qkhalf.h) is built for dim = 64 * num_heads with
 "RoPE2d" at "fast" / "parity" precision; with kv_merge_attn, "RoPE2dV2", dim = 128 * num_heads or fp8 / mxfp8 it raises.  text_loss=True (every
 block a full dual block, `out_text_proj` on the final text stream, forward returns (v, txt_pred); include/mmdit_hip_textloss.h is the trainer's
-masked loss) composes with every option above except kv_merge_attn, with which it raises.  The arithmetic of forward() and of
+masked loss) composes with every option above except kv_merge_attn, with which it raises.  attn_type="cosine2" (L2-normalised queries / keys,
+weights (q . k + 1) / sum evaluated in linear time; no q_norm_* / k_norm_* weights in the state dict; include/mmdit_hip_cos2.h) is built for
+dim = 64 * num_heads with "RoPE2d" at "fast" / "parity" precision; with kv_merge_attn, qk_half_dim, text_loss, "RoPE2dV2", another head width
+or fp8 / mxfp8 it raises.  The arithmetic of forward() and of
 its backward runs in libmmdit_hip.so through sd3_amd.engine; there is no PyTorch/CPU fallback.
 """
 import json
@@ -72,7 +75,7 @@ class _MMDiTFn(torch.autograd.Function):
 class diff_model(nn.Module):
     # inCh - number of latent channels; class_dim - pooled text embedding width; patch_size - 2;
     # dim / hidden_scale / num_heads / num_blocks - transformer geometry (dim = 64*num_heads, or 128*num_heads);
-    # attn_type - "softmax" | "softmax_flash"; MLP_type - "swiglu" | "gelu"; positional_encoding - "RoPE2d" | "RoPE2dV2";
+    # attn_type - "softmax" | "softmax_flash" | "cosine2" (dim = 64*num_heads, "RoPE2d", none of the three options below); MLP_type - "swiglu" | "gelu"; positional_encoding - "RoPE2d" | "RoPE2dV2";
     # qk_half_dim - queries / keys projected to dim / 2 (dim = 64*num_heads, "RoPE2d", no kv_merge_attn);
     # text_loss - full last block + out_text_proj head, forward returns (v, txt_pred) (no kv_merge_attn)
     def __init__(self, inCh, class_dim, patch_size, dim, hidden_scale, num_heads, attn_type, MLP_type, num_blocks, device, positional_encoding,
@@ -105,6 +108,15 @@ class diff_model(nn.Module):
         if self.qk_half_dim and (dim % num_heads or dim // num_heads != 64):
             raise RuntimeError(f"diff_model (HIP path): qk_half_dim is built for dim = 64 * num_heads only (32-wide queries / keys, 64-wide values), "
                                f"but got dim={dim}, num_heads={num_heads}")
+        self.cos2 = attn_type == "cosine2"
+        if self.cos2:
+            for on, what, why in ((self.kv_merge_attn, "kv_merge_attn", "the linear-time kernels sum over every key and have no pair-averaging form"),
+                                  (self.qk_half_dim, "qk_half_dim", "the kernels keep a 64 x 64 state per head: queries, keys and values are 64 wide"),
+                                  (bool(text_loss), "text_loss", "the last block of a text_loss model attends for its text queries too, a form the cosine2 path was never run in"),
+                                  (positional_encoding == "RoPE2dV2", "positional_encoding='RoPE2dV2'", "mmdit_qk_l2norm_rope_fwd / _bwd rotate channel pairs"),
+                                  (bool(dim % num_heads) or dim // num_heads != 64, f"dim={dim}, num_heads={num_heads}", "it is built for dim = 64 * num_heads only")):
+                if on:
+                    raise RuntimeError(f"diff_model (HIP path): attn_type='cosine2' is not built with {what} ({why})")
         if self.kv_merge_attn and positional_encoding == "RoPE2dV2":
             raise RuntimeError("diff_model (HIP path): kv_merge_attn is not built for positional_encoding='RoPE2dV2' (no pair-averaging form of "
                                "mmdit_qk_norm_rope3_fwd / _bwd); use 'RoPE2d' with kv_merge_attn, or RoPE2dV2 without it")
@@ -205,6 +217,9 @@ class diff_model(nn.Module):
         if precision in ("fp8", "mxfp8") and self.qk_half_dim:
             raise RuntimeError(f"set_precision('{precision}'): qk_half_dim has no e4m3 path (the QKV epilogue, mmdit_attn_fwd_mx and mmdit_attn_fwd_e4m3 take "
                                "64-wide queries and keys); use 'fast' or 'parity'")
+        if precision in ("fp8", "mxfp8") and self.cos2:
+            raise RuntimeError(f"set_precision('{precision}'): attn_type='cosine2' has no e4m3 path (the QKV epilogue, mmdit_attn_fwd_mx and mmdit_attn_fwd_e4m3 are "
+                               "softmax attention behind an RMSNorm); use 'fast' or 'parity'")
         if attention not in ("bf16", "e4m3"):
             raise ValueError(f"set_precision: attention must be 'bf16' or 'e4m3', got {attention!r}")
         if attention == "e4m3" and precision not in ("fp8", "mxfp8"):

@@ -863,6 +863,130 @@ def attn_bwd_qkhalf(Q, K, V, Ox, Oc, dOx, dOc, lse, n_img, scale, out_dtype):
     return dQ, dK, dV
 
 
+def _qk_l2(fn, streams, batch, heads, s_total, T3, out_dtype=None):
+    """One launch of a cosine2 row kernel (include/mmdit_hip_cos2.h) over a list of 1 or 2 streams = (qkv, rope_cos, rope_sin, tokens, tok0): there
+    are no norm weights.  T3 = (Q, K, V) of a forward (written, bfloat16 or float32), (dQ, dK, dV) of a backward (out_dtype = the dtype of the
+    returned dqkv).  The row width 3 * heads * 64 and the table width (tokens, 64) are checked here, before the launch: the kernel indexes both
+    by the head width."""
+    hd = _lib.COS2_HEAD_DIM
+    bwd = out_dtype is not None
+    for t in T3:
+        if tuple(t.shape) != (batch, heads, s_total, hd) or t.dtype != T3[0].dtype or t.dtype not in (torch.bfloat16, torch.float32):
+            raise RuntimeError(f"{fn}: {'dQ / dK / dV' if bwd else 'Q / K / V'} are (batch, heads, s_total, {hd}) = {(batch, heads, s_total, hd)} of one dtype "
+                               f"(bfloat16 or float32), got {t.dtype} {tuple(t.shape)}")
+        _c(t)
+    if bwd and out_dtype not in (torch.bfloat16, torch.float32):
+        raise RuntimeError(f"{fn}: dqkv is bfloat16 or float32, got {out_dtype}")
+    if len(streams) not in (1, 2):
+        raise RuntimeError(f"{fn}: a launch takes 1 or 2 streams, got {len(streams)}")
+    probs, outs = (_lib.QkProblem * len(streams))(), []
+    for q, st in zip(probs, streams):
+        qkv, rc, rs, tokens, tok0 = st
+        if qkv.dim() != 2 or tuple(qkv.shape) != (batch * tokens, 3 * heads * hd) or qkv.dtype not in (torch.bfloat16, torch.float32):
+            raise RuntimeError(f"{fn}: qkv rows are bfloat16 or float32 (batch * tokens, 3 * heads * {hd}) = {(batch * tokens, 3 * heads * hd)}, got {qkv.dtype} {tuple(qkv.shape)}")
+        if (rc is None) != (rs is None):
+            raise RuntimeError(f"{fn}: the cos and the sin table come together (or neither: the text stream)")
+        for tb in (rc, rs):
+            if tb is not None and (tuple(tb.shape) != (tokens, hd) or tb.dtype != torch.float32):
+                raise RuntimeError(f"{fn}: the RoPE tables are fp32 (tokens, {hd}) = {(tokens, hd)}, got {tb.dtype} {tuple(tb.shape)}")
+            if tb is not None:
+                _c(tb)
+        if tokens < 1 or tok0 < 0 or tok0 + tokens > s_total:
+            raise RuntimeError(f"{fn}: tokens [{tok0}, {tok0 + tokens}) are outside the joint sequence of {s_total}")
+        q.qkv, q.wq, q.wk, q.rope_cos, q.rope_sin, q.tokens, q.tok0 = _p(_c(qkv)), None, None, _p(rc), _p(rs), tokens, tok0
+        if bwd:
+            dqkv = torch.empty(qkv.shape, dtype=out_dtype, device=qkv.device)
+            q.dqkv, q.dwq, q.dwk = _p(dqkv), None, None
+            outs.append(dqkv)
+    if any(st[0].dtype != streams[0][0].dtype for st in streams):
+        raise RuntimeError(f"{fn}: the streams of one launch share the qkv dtype")
+    a, b, c = (_p(t) for t in T3)
+    launch, qkv_dt = getattr(_lib.lib(), fn), _dt(streams[0][0])
+    if not bwd:
+        check(launch(probs, len(streams), qkv_dt, _dt(T3[0]), batch, heads, s_total, a, b, c, _s()), fn)
+    else:
+        check(launch(probs, len(streams), a, b, c, _dt(T3[0]), qkv_dt, _DT[out_dtype], batch, heads, s_total, _s()), fn)
+    return outs
+
+
+def qk_l2norm_rope_fwd_pair(img, txt, batch, heads, s_total, Q, K, V):
+    """attn_type="cosine2": per-head L2 normalisation x / max(||x||, 1e-12) + axial RoPE + head split of the image and the text rows of a block in
+    one launch (mmdit_qk_l2norm_rope_fwd).  img / txt = (qkv, rope_cos, rope_sin, tokens, tok0) -- the text stream's tables are None --, txt may be
+    None (one stream); both write the joint Q / K / V (batch, heads, s_total, 64), bfloat16 or float32."""
+    _qk_l2("mmdit_qk_l2norm_rope_fwd", [st for st in (img, txt) if st is not None], batch, heads, s_total, (Q, K, V))
+
+
+def qk_l2norm_rope_bwd_pair(dQ, dK, dV, img, txt, batch, heads, s_total, out_dtype):
+    """Backward of both streams in one launch (mmdit_qk_l2norm_rope_bwd); the argument tuples of qk_l2norm_rope_fwd_pair.  Returns the list of
+    dqkv, one per stream given.  No weight gradient."""
+    return _qk_l2("mmdit_qk_l2norm_rope_bwd", [st for st in (img, txt) if st is not None], batch, heads, s_total, (dQ, dK, dV), out_dtype)
+
+
+def _cos2_operands(Q, K, V, n_img, what):
+    """Checks of the cosine2 attention launches: contiguous Q, K, V (batch, heads, S, 64) of one dtype, bfloat16 or float32."""
+    hd = _lib.COS2_HEAD_DIM
+    if Q.dim() != 4 or Q.shape[-1] != hd:
+        raise RuntimeError(f"{what}: Q is (batch, heads, S, {hd}), got {tuple(Q.shape)}")
+    for t in (K, V):
+        if t.shape != Q.shape or t.dtype != Q.dtype:
+            raise RuntimeError(f"{what}: Q, K, V share one shape (batch, heads, S, {hd}) and dtype, got {t.dtype} {tuple(t.shape)} beside {Q.dtype} {tuple(Q.shape)}")
+    if Q.dtype not in (torch.bfloat16, torch.float32):
+        raise RuntimeError(f"{what}: the operands are bfloat16 or float32, got {Q.dtype}")
+    for t in (Q, K, V):
+        _c(t)
+    batch, heads, S, _ = Q.shape
+    if S < 1 or not 0 <= n_img <= S:
+        raise RuntimeError(f"{what}: S >= 1 and 0 <= n_img <= S = {S}, got n_img={n_img}")
+    return batch, heads, S
+
+
+def _cos2_ws(batch, heads, S, device):
+    return torch.empty(_lib.lib().mmdit_attn_cos2_ws_bytes(batch, heads, S) // 4, dtype=torch.float32, device=device)
+
+
+def attn_cos2_fwd(Q, K, V, n_img):
+    """attn_type="cosine2": out_i = sum_j (q_i . k_j + 1) v_j / sum_j (q_i . k_j + 1) in linear time (mmdit_attn_cos2_fwd).  Q, K, V
+    (batch, heads, S, 64) bfloat16 or float32; returns Ox (batch, n_img, heads * 64), Oc (batch, S - n_img, heads * 64) in the operands' dtype
+    (None for an empty stream) and den fp32 (batch, heads, S)."""
+    batch, heads, S = _cos2_operands(Q, K, V, n_img, "attn_cos2_fwd")
+    D = heads * _lib.COS2_HEAD_DIM
+    Ox = torch.empty((batch, n_img, D), dtype=Q.dtype, device=Q.device) if n_img > 0 else None
+    Oc = torch.empty((batch, S - n_img, D), dtype=Q.dtype, device=Q.device) if S > n_img else None
+    den = torch.empty((batch, heads, S), dtype=torch.float32, device=Q.device)
+    ws = _cos2_ws(batch, heads, S, Q.device)
+    check(_lib.lib().mmdit_attn_cos2_fwd(_p(Q), _p(K), _p(V), _dt(Q), batch, heads, S, n_img, _p(Ox), _p(Oc), _dt(Q), _p(den), _p(ws), _s()), "mmdit_attn_cos2_fwd")
+    return Ox, Oc, den
+
+
+def attn_cos2_bwd(Q, K, V, Ox, Oc, dOx, dOc, den, n_img, out_dtype):
+    """Backward of attn_cos2_fwd (mmdit_attn_cos2_bwd): dQ, dK, dV (batch, heads, S, 64) in out_dtype; O / dO in the operands' dtype, dOc None = zeros."""
+    batch, heads, S = _cos2_operands(Q, K, V, n_img, "attn_cos2_bwd")
+    if out_dtype not in (torch.bfloat16, torch.float32) or (Q.dtype == torch.float32 and out_dtype != torch.float32):
+        raise RuntimeError(f"attn_cos2_bwd: gradients are bfloat16 or float32 (float32 for float32 operands), got {out_dtype}")
+    D = heads * _lib.COS2_HEAD_DIM
+    for t, rows, name in ((Ox, n_img, "Ox"), (dOx, n_img, "dOx"), (Oc, S - n_img, "Oc"), (dOc, S - n_img, "dOc")):
+        if t is None and (rows == 0 or name == "dOc" or (name == "Oc" and dOc is None)):
+            continue
+        # (the engine hands the streams over as (batch * tokens, heads * 64) rows: the same memory)
+        if t is None or t.dtype != Q.dtype or t.shape[-1] != D or t.numel() != batch * rows * D:
+            raise RuntimeError(f"attn_cos2_bwd: {name} is {Q.dtype} (batch, tokens, heads * {_lib.COS2_HEAD_DIM}) = {(batch, rows, D)}, got "
+                               f"{None if t is None else (t.dtype, tuple(t.shape))}")
+        _c(t)
+    if den.dtype != torch.float32 or tuple(den.shape) != (batch, heads, S):
+        raise RuntimeError(f"attn_cos2_bwd: den is fp32 (batch, heads, S) = {(batch, heads, S)}, got {den.dtype} {tuple(den.shape)}")
+    dQ = torch.empty(Q.shape, dtype=out_dtype, device=Q.device)
+    dK = torch.empty(Q.shape, dtype=out_dtype, device=Q.device)
+    dV = torch.empty(Q.shape, dtype=out_dtype, device=Q.device)
+    ws = _cos2_ws(batch, heads, S, Q.device)
+    if n_img == 0:
+        Ox = dOx = None
+    if n_img == S:
+        Oc = dOc = None
+    check(_lib.lib().mmdit_attn_cos2_bwd(_p(Q), _p(K), _p(V), _dt(Q), _p(Ox), _p(Oc), _p(dOx), _p(dOc), _dt(Q), _p(_c(den)), batch, heads, S, n_img,
+                                         _p(dQ), _p(dK), _p(dV), _DT[out_dtype], _p(ws), _s()), "mmdit_attn_cos2_bwd")
+    return dQ, dK, dV
+
+
 def _merge_status(status, what):
     if status == _lib.ERR_SHAPE:
         raise RuntimeError(f"{what}: kv_merge_attn averages adjacent token pairs -- the tokens of each stream, its offset and the joint length must be even")
