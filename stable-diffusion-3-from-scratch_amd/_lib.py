@@ -22,6 +22,7 @@ HEADER_ROPE3_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_rope3.h")   
 HEADER_QKHALF_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_qkhalf.h")   # the qk_half_dim entry points, outside it as well
 HEADER_TEXTLOSS_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_textloss.h")   # the text_loss entry point, outside it as well
 HEADER_COS2_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_cos2.h")   # the attn_type="cosine2" entry points, outside it as well
+HEADER_FP8PAD_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_fp8pad.h")   # the zero-padded e4m3 quantisers, outside it as well
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_SILU, ACT_SWIGLU, ACT_SWIGLU_BWD = 0, 1, 2, 3
@@ -187,6 +188,12 @@ _COS2_SIGNATURES = {
     "mmdit_attn_cos2_fwd": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp], _i),
     "mmdit_attn_cos2_bwd": ([_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp], _i),
 }
+# entry points of include/mmdit_hip_fp8pad.h (fp8 / mxfp8 inference at K % 128 == 64: e4m3 codes in rows zero-padded to the 128-wide K tile)
+_FP8PAD_SIGNATURES = {
+    "mmdit_fp8_quantize_pad": ([_vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp], _i),
+    "mmdit_fp8_quantize_delayed_pad": ([_vp, _i, _i, _i, _i64, _vp, _i, ctypes.c_float, _vp, _vp], _i),
+    "mmdit_mxfp8_quantize_pad": ([_vp, _i, _i, _i, _i64, _vp, _vp, _vp], _i),
+}
 COS2_HEAD_DIM = 64                                     # MMDIT_COS2_HEAD_DIM
 ATTN_COS2_TOKEN_CHUNK, ATTN_COS2_ROW_TILE = 128, 64    # MMDIT_ATTN_COS2_TOKEN_CHUNK / MMDIT_ATTN_COS2_ROW_TILE
 HEAD_DIMS = (64, 128)                                  # head widths the attention and QK-norm / RoPE kernels are built for
@@ -248,6 +255,13 @@ def declared_cos2_symbols():
     return sorted(set(re.findall(r"\b(mmdit_[a-z0-9_]+)\s*\(", txt)) - {"mmdit_stream_t"})
 
 
+def declared_fp8pad_symbols():
+    """Entry points declared by include/mmdit_hip_fp8pad.h (parsed the same way)."""
+    with open(HEADER_FP8PAD_PATH) as f:
+        txt = f.read()
+    return sorted(set(re.findall(r"\b(mmdit_[a-z0-9_]+)\s*\(", txt)) - {"mmdit_stream_t"})
+
+
 def lib():
     """Load the HIP library (once).  Raises RuntimeError if it is not built."""
     global _lib
@@ -266,7 +280,7 @@ def lib():
             pass
         L = ctypes.CDLL(LIB_PATH)
         for name, (argtypes, restype) in (list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_HD128_SIGNATURES.items()) + list(_ROPE3_SIGNATURES.items())
-                                          + list(_QKHALF_SIGNATURES.items()) + list(_TEXTLOSS_SIGNATURES.items()) + list(_COS2_SIGNATURES.items())):
+                                          + list(_QKHALF_SIGNATURES.items()) + list(_TEXTLOSS_SIGNATURES.items()) + list(_COS2_SIGNATURES.items()) + list(_FP8PAD_SIGNATURES.items())):
             fn = getattr(L, name)  # AttributeError -> symbol missing: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

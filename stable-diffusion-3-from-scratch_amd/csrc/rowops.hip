@@ -3,6 +3,7 @@
 // per-batch / per-column gradient sums are accumulated in registers over a row chunk and
 // flushed with fp32 atomics (caller zero-initialises the destination).
 #include "qk_rows.h"
+#include "fp8_quant.h"
 #include "../../include/mmdit_hip_hd128.h"
 
 namespace {
@@ -1521,19 +1522,13 @@ __global__ __launch_bounds__(256) void fp8_amax_kernel(const TI* __restrict__ x,
 }
 template <typename TI>
 __global__ __launch_bounds__(256) void fp8_quant_kernel(const TI* __restrict__ x, int64_t n8, const float* __restrict__ amax, uint2* __restrict__ q, float* __restrict__ scale) {
-  const float a = fmaxf(amax[0], 1e-12f), s = 448.f / a;
-  if (blockIdx.x == 0 && threadIdx.x == 0) scale[0] = a / 448.f;
+  float dq;
+  const float s = fp8_range(amax[0], dq);
+  if (blockIdx.x == 0 && threadIdx.x == 0) scale[0] = dq;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
     float v[8];
     ld8(x + i * 8, v);
-#pragma unroll
-    for (int e = 0; e < 8; e++) v[e] = fminf(fmaxf(v[e] * s, -448.f), 448.f);
-    int lo = 0, hi = 0;
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], lo, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], lo, true);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], hi, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], hi, true);
-    q[i] = make_uint2((unsigned)lo, (unsigned)hi);
+    q[i] = fp8_pack8(v, s);
   }
 }
 // Delayed scaling (one pass): quantise with the amax of the PREVIOUS call at this call site (x margin) while collecting this
@@ -1543,53 +1538,26 @@ template <typename TI>
 __global__ __launch_bounds__(256) void fp8_quant_delayed_kernel(const TI* __restrict__ x, int64_t n8, float* __restrict__ state, int phase, float margin,
                                                                 uint2* __restrict__ q) {
   __shared__ float sm[4];
-  const float a = fmaxf(state[phase % 3] * margin, 1e-12f), s = 448.f / a;
-  if (blockIdx.x == 0 && threadIdx.x == 0) { state[3] = a / 448.f; state[(phase + 2) % 3] = 0.f; }
+  float dq;
+  const float s = fp8_range(state[phase % 3] * margin, dq);
+  if (blockIdx.x == 0 && threadIdx.x == 0) { state[3] = dq; state[(phase + 2) % 3] = 0.f; }
   float m = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
     float v[8];
     ld8(x + i * 8, v);
-#pragma unroll
-    for (int e = 0; e < 8; e++) { m = fmaxf(m, fabsf(v[e])); v[e] = fminf(fmaxf(v[e] * s, -448.f), 448.f); }
-    int lo = 0, hi = 0;
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], lo, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], lo, true);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], hi, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], hi, true);
-    q[i] = make_uint2((unsigned)lo, (unsigned)hi);
+    m = fp8_amax8(m, v);
+    q[i] = fp8_pack8(v, s);
   }
-  m = wave_max(m);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicMax((unsigned int*)(state + (phase + 1) % 3), __float_as_uint(fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]))));
+  fp8_wg_amax(m, state + (phase + 1) % 3, sm);
 }
 }  // namespace
 
 namespace {
 // MX quantisation: one thread per 32-element block (64 B of bf16 / 128 B of fp32 in, 32 B + 1 scale byte out); consecutive
-// threads take consecutive blocks of a row, so the loads and the e4m3 stores of a wave are contiguous.
+// threads take consecutive blocks of a row, so the loads and the e4m3 stores of a wave are contiguous.  (The block itself: fp8_quant.h.)
 template <typename TI>
 __global__ __launch_bounds__(256) void mxfp8_quant_kernel(const TI* __restrict__ x, int rows, int K, int64_t ldx, uint4* __restrict__ q, unsigned char* __restrict__ sc) {
-  const int bpr = K >> 5;                                             // blocks per row
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= (int64_t)rows * bpr) return;
-  const int row = (int)(t / bpr), blk = (int)(t - (int64_t)row * bpr);
-  const TI* src = x + (int64_t)row * ldx + blk * 32;
-  float v[32];
-#pragma unroll
-  for (int c = 0; c < 4; c++) ld8(src + c * 8, *(float(*)[8])(v + c * 8));
-  float amax = 0.f;
-#pragma unroll
-  for (int e = 0; e < 32; e++) amax = fmaxf(amax, fabsf(v[e]));
-  float inv;
-  const int ex = mx_exponent(amax, inv);
-  unsigned w[8];
-#pragma unroll
-  for (int c = 0; c < 8; c++) w[c] = mx_pack4(v + 4 * c, inv);
-  uint4* dst = q + ((int64_t)row * K + blk * 32) / 16;
-  dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
-  dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
-  sc[mx_scale_index(row, blk, rows)] = (unsigned char)(ex + 127);
+  mx_quant_block((int64_t)blockIdx.x * 256 + threadIdx.x, x, rows, K, K, ldx, q, sc);
 }
 }  // namespace
 

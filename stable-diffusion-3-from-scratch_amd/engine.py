@@ -67,26 +67,28 @@ def _gemm(m, A, B, **kw):
 
 def _to_fp8(m, p):
     """fp8 inference mode: quantise the activation on the fly (per-tensor amax -> e4m3), take the cached e4m3 copy of the
-    weight, drop the backward-only aux output.  Problems whose K is not a multiple of the 128-wide fp8 K-tile stay bf16."""
+    weight, drop the backward-only aux output.  K % 128 == 64 (dim = 64 * heads with an odd head count): the quantisers write both operands
+    into rows zero-padded to ops.fp8_k_pad(K), the next multiple of the e4m3 kernels' 128-wide K tile, and the GEMM runs on that K -- a zero
+    code times anything is zero, the product is exact.  Only problems whose K is no multiple of 64 stay bf16."""
     A, B = p["A"], p["B"]
     pre = isinstance(A, ops.MxAct)       # the producer already emitted MX e4m3 (block_fwd checked the site's eligibility)
-    if not pre and (A.dtype != BF16 or B.dtype != BF16 or A.shape[1] % 128 or p.get("a_kmajor") or p.get("b_kmajor")):
+    if not pre and (A.dtype != BF16 or B.dtype != BF16 or ops.fp8_k_pad(A.shape[1]) is None or p.get("a_kmajor") or p.get("b_kmajor")):
         return p
     ent, gen = m._q.get(id(B)), getattr(B, "_mmdit_gen", 0)     # (the bf16 copy is refreshed in place: packing.Pack.generation)
     if m.mx:    # MX: block scales, stateless one-pass quantisation of the activation
         if not pre and not A.is_contiguous():
             return p
         if ent is None or ent[4] != gen:
-            qb, sb = ops.quant_mxfp8(B)
+            qb, sb = ops.quant_mxfp8(B, pad=True)
             ent = m._q[id(B)] = (B, qb, sb, None, gen)
-        qa, sa = (A.q, A.sc) if pre else ops.quant_mxfp8(A)
+        qa, sa = (A.q, A.sc) if pre else ops.quant_mxfp8(A, pad=True)
         q = {k: v for k, v in p.items() if k != "aux"}
         q.update(A=qa, B=ent[1], scale_a=sa, scale_b=ent[2], scale_mode=1)
         return q
     if ent is None or ent[4] != gen:
-        qb, sb = ops.quant_fp8(B)
+        qb, sb = ops.quant_fp8(B, pad=True)
         ent = m._q[id(B)] = (B, qb, sb, ent[3] if ent is not None else ops.Fp8Site(), gen)
-    qa, sa = ent[3].quantise(A)      # delayed scaling: consecutive sampler steps see nearly the same activation range
+    qa, sa = ent[3].quantise(A, pad=True)      # delayed scaling: consecutive sampler steps see nearly the same activation range
     q = {k: v for k, v in p.items() if k != "aux"}
     q.update(A=qa, B=ent[1], scale_a=sa, scale_b=ent[2])
     return q

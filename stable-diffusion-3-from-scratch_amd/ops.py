@@ -325,13 +325,31 @@ def gemm(A, B, **kw):
     return gemm_grouped([dict(A=A, B=B, **kw)])[0]
 
 
-def quant_fp8(x):
-    """Per-tensor e4m3 quantisation: returns (q: torch.float8_e4m3fn like x, scale: fp32 (1,) dequantisation scale on the device)."""
+def fp8_k_pad(K):
+    """Width of the e4m3 GEMM operand made from a K-wide row-major operand: K rounded up to the kernels' 128-wide K tile (K itself when
+    K % 128 == 0), or None when the operand is not eligible (K % 64 != 0: the zero pad is written in whole 64-byte halves of a tile)."""
+    return None if K <= 0 or K % 64 else (K + 127) // 128 * 128
+
+
+def _pads(x, pad):
+    """pad=True and a 2-D operand with K % 128 == 64: the quantiser writes rows zero-padded to fp8_k_pad(K) (include/mmdit_hip_fp8pad.h)."""
+    return bool(pad) and x.dim() == 2 and x.shape[1] % 128 == 64
+
+
+def quant_fp8(x, pad=False):
+    """Per-tensor e4m3 quantisation: returns (q: torch.float8_e4m3fn like x, scale: fp32 (1,) dequantisation scale on the device).
+    pad=True: a 2-D x with K % 128 == 64 gives q (rows, fp8_k_pad(K)), the columns behind K zero codes (mmdit_fp8_quantize_pad): the form
+    the e4m3 GEMM takes when both operands are padded (engine._to_fp8).  Every other x as without it."""
     n = x.numel()
     buf = torch.zeros(2, dtype=torch.float32, device=x.device)       # [amax, scale]
-    q = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
     L = _lib.lib()
     check(L.mmdit_fp8_amax(_p(_c(x)), _dt(x), n, _p(buf), _s()), "mmdit_fp8_amax")
+    if _pads(x, pad):
+        rows, K = x.shape
+        q = torch.empty((rows, fp8_k_pad(K)), dtype=torch.float8_e4m3fn, device=x.device)
+        check(L.mmdit_fp8_quantize_pad(_p(x), _dt(x), rows, K, K, _p(buf), _p(q), _p(buf[1:]), _s()), "mmdit_fp8_quantize_pad")
+        return q, buf[1:]
+    q = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
     check(L.mmdit_fp8_quantize(_p(x), _dt(x), n, _p(buf), _p(q), _p(buf[1:]), _s()), "mmdit_fp8_quantize")
     return q, buf[1:]
 
@@ -431,10 +449,17 @@ def attn_fwd_e4m3(Q, K, V, n_img, scale, mx=False):
     return Ox, Oc
 
 
-def quant_mxfp8(x):
+def quant_mxfp8(x, pad=False):
     """MX (OCP microscaling) e4m3 quantisation of a row-major 2-D operand: returns (q: float8_e4m3fn like x, scales: uint8 E8M0 block
-    scales in the GEMM's layout, see mx_scales_to_rows; 512 spare bytes behind them) -- mmdit_mxfp8_quantize; pass scale_mode=1 to gemm()."""
+    scales in the GEMM's layout, see mx_scales_to_rows; 512 spare bytes behind them) -- mmdit_mxfp8_quantize; pass scale_mode=1 to gemm().
+    pad=True: K % 128 == 64 gives q (rows, fp8_k_pad(K)) with zero codes behind column K and the scales of a (rows, fp8_k_pad(K)) operand,
+    the pad blocks' the all-zero-block code (mmdit_mxfp8_quantize_pad); every other K as without it."""
     rows, K = x.shape
+    if _pads(x, pad):
+        Kp = fp8_k_pad(K)
+        q, sc = _mx_buffers(rows, Kp, x.device)
+        check(_lib.lib().mmdit_mxfp8_quantize_pad(_p(x), _dt(x), rows, K, x.stride(0), _p(q), _p(sc), _s()), "mmdit_mxfp8_quantize_pad")
+        return q, sc
     q = torch.empty((rows, K), dtype=torch.float8_e4m3fn, device=x.device)
     sc = torch.empty(mx_scale_bytes(rows, K), dtype=torch.uint8, device=x.device)
     check(_lib.lib().mmdit_mxfp8_quantize(_p(x), _dt(x), rows, K, x.stride(0), _p(q), _p(sc), _s()), "mmdit_mxfp8_quantize")
@@ -448,13 +473,22 @@ class Fp8Site:
     def __init__(self, margin=1.5):
         self.state, self.phase, self.margin = None, 0, margin
 
-    def quantise(self, x):
+    def quantise(self, x, pad=False):
+        """pad=True: a 2-D x with K % 128 == 64 is quantised into rows zero-padded to fp8_k_pad(K) (mmdit_fp8_quantize_delayed_pad: the
+        same state, the same amax); every other x as without it."""
         L = _lib.lib()
-        q = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
         if self.state is None:
             self.state = torch.zeros(4, dtype=torch.float32, device=x.device)
             check(L.mmdit_fp8_amax(_p(_c(x)), _dt(x), x.numel(), _p(self.state), _s()), "mmdit_fp8_amax")      # -> state[0] = amax
-        check(L.mmdit_fp8_quantize_delayed(_p(_c(x)), _dt(x), x.numel(), _p(self.state), self.phase, float(self.margin if self.phase else 1.0),
+        margin = float(self.margin if self.phase else 1.0)
+        if _pads(x, pad):
+            rows, K = x.shape
+            q = torch.empty((rows, fp8_k_pad(K)), dtype=torch.float8_e4m3fn, device=x.device)
+            check(L.mmdit_fp8_quantize_delayed_pad(_p(_c(x)), _dt(x), rows, K, K, _p(self.state), self.phase, margin, _p(q), _s()), "mmdit_fp8_quantize_delayed_pad")
+            self.phase += 1
+            return q, self.state[3:]
+        q = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
+        check(L.mmdit_fp8_quantize_delayed(_p(_c(x)), _dt(x), x.numel(), _p(self.state), self.phase, margin,
                                            _p(q), _s()), "mmdit_fp8_quantize_delayed")
         self.phase += 1
         return q, self.state[3:]
