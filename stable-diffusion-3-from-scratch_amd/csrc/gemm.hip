@@ -307,6 +307,7 @@ static constexpr PlannerSwitches planner_switches() { return {}; }
 
 // Tile-configuration heuristic of the LDS-DMA path.  Bigger tiles halve the L2->CU traffic per FLOP (a 128x128
 // tile needs ~64 B/clk/CU at full MFMA rate, about what the L2 can deliver) but need enough tiles to fill the `cu` compute units.
+// (restated for bf16 launches without split as pick_cfg in tests/test_qkv_epilogue_edges_gpu.py)
 static int pick_dma_cfg(const mmdit_gemm_args* args, int count, int split_k, bool stream_k, bool lean_ok, long cu) {
   const PlannerSwitches& sw = planner_switches();
   if (sw.cfg >= 0) return sw.cfg == CFG_320x256 && !lean_ok ? CFG_256x256 : sw.cfg;
@@ -419,6 +420,8 @@ static int choose_kernel(const mmdit_gemm_args* args, int count, const QkRequest
     if (swiglu_bwd) cfg = CFG_256x256;                     // (the fused backward epilogue exists at 256 rows)
     // (MX operands + the QKV epilogue: the 8-phase kernel's 256-row tile; bf16: the same kernel when tiles are CLAIMED -- since round 6 it takes
     // the wide-slot kernel's time, 131 us at MMDiT-B, and its 927 tiles are then immune to held compute units like the other multi-round launches)
+    // (this rule, the refusals of the qkr block below, the kernel of a fused launch and its tile walk are restated as fused_path in
+    // tests/test_qkv_epilogue_edges_gpu.py)
     if (qkr && (fp8 || sw.qk8 || ds.claiming)) cfg = CFG_256x256;
     dma_cfg_tile(cfg, bm, bn);
   }
@@ -586,6 +589,7 @@ static int choose_kernel(const mmdit_gemm_args* args, int count, const QkRequest
   pl->code = dma ? (cfg | (gp.stream_k ? 16 : 0) | (tail_mode ? 32 : 0) | (lean || wgrad8 ? 128 : 0) | (p8 || conv8 ? 256 : 0)) : 64;
   // a persistent launch of the 8-phase kernel with 256-row tiles and more positions than the budget's workgroups CLAIMS its tiles when claiming is on
   // and the workspace is registered (gemm8p.hip); e4m3-operand and convolution launches, and the statically balanced tail, keep the static walk
+  // (for the fused QKV launch restated in fused_path, tests/test_qkv_epilogue_edges_gpu.py: "claimed" / "multi" / "single")
   const bool claimed = pl->kernel == KERNEL_8P && !mx8 && cfg == CFG_256x256 && gp.persistent && gp.tail_first < 0 && total_work(gp) > pl->cu;
   pl->sched_page = claimed && ds.ws && ds.claiming ? (int*)((char*)ds.ws + 4096) : nullptr;
   return 0;
