@@ -23,6 +23,7 @@ HEADER_QKHALF_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_qkhalf.h") 
 HEADER_TEXTLOSS_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_textloss.h")   # the text_loss entry point, outside it as well
 HEADER_COS2_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_cos2.h")   # the attn_type="cosine2" entry points, outside it as well
 HEADER_FP8PAD_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_fp8pad.h")   # the zero-padded e4m3 quantisers, outside it as well
+HEADER_MXPAD_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_mxpad.h")   # the MX producers on zero-padded rows, outside it as well
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_SILU, ACT_SWIGLU, ACT_SWIGLU_BWD = 0, 1, 2, 3
@@ -194,6 +195,13 @@ _FP8PAD_SIGNATURES = {
     "mmdit_fp8_quantize_delayed_pad": ([_vp, _i, _i, _i, _i64, _vp, _i, ctypes.c_float, _vp, _vp], _i),
     "mmdit_mxfp8_quantize_pad": ([_vp, _i, _i, _i, _i64, _vp, _vp, _vp], _i),
 }
+# entry points of include/mmdit_hip_mxpad.h ("mxfp8" inference at d % 128 == 64: the MX-emitting adaLN / attention kernels writing rows zero-padded
+# to the 128-wide K tile); the attention forms take the argument lists of their unpadded namesakes
+_MXPAD_SIGNATURES = {
+    "mmdit_ln_modulate_fwd_mx_pad": ([ctypes.POINTER(LnFwdProblem), _i, _i, _i, _vp, _vp, _vp], _i),
+    "mmdit_attn_fwd_mx_pad": _SIGNATURES["mmdit_attn_fwd_mx"],
+    "mmdit_attn_fwd_e4m3_mx_pad": _EXT_SIGNATURES["mmdit_attn_fwd_e4m3"],
+}
 COS2_HEAD_DIM = 64                                     # MMDIT_COS2_HEAD_DIM
 ATTN_COS2_TOKEN_CHUNK, ATTN_COS2_ROW_TILE = 128, 64    # MMDIT_ATTN_COS2_TOKEN_CHUNK / MMDIT_ATTN_COS2_ROW_TILE
 HEAD_DIMS = (64, 128)                                  # head widths the attention and QK-norm / RoPE kernels are built for
@@ -262,6 +270,13 @@ def declared_fp8pad_symbols():
     return sorted(set(re.findall(r"\b(mmdit_[a-z0-9_]+)\s*\(", txt)) - {"mmdit_stream_t"})
 
 
+def declared_mxpad_symbols():
+    """Entry points declared by include/mmdit_hip_mxpad.h (parsed the same way)."""
+    with open(HEADER_MXPAD_PATH) as f:
+        txt = f.read()
+    return sorted(set(re.findall(r"\b(mmdit_[a-z0-9_]+)\s*\(", txt)) - {"mmdit_stream_t"})
+
+
 def lib():
     """Load the HIP library (once).  Raises RuntimeError if it is not built."""
     global _lib
@@ -280,7 +295,7 @@ def lib():
             pass
         L = ctypes.CDLL(LIB_PATH)
         for name, (argtypes, restype) in (list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_HD128_SIGNATURES.items()) + list(_ROPE3_SIGNATURES.items())
-                                          + list(_QKHALF_SIGNATURES.items()) + list(_TEXTLOSS_SIGNATURES.items()) + list(_COS2_SIGNATURES.items()) + list(_FP8PAD_SIGNATURES.items())):
+                                          + list(_QKHALF_SIGNATURES.items()) + list(_TEXTLOSS_SIGNATURES.items()) + list(_COS2_SIGNATURES.items()) + list(_FP8PAD_SIGNATURES.items()) + list(_MXPAD_SIGNATURES.items())):
             fn = getattr(L, name)  # AttributeError -> symbol missing: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

@@ -9,6 +9,7 @@
 // Backward: two kernels (dQ: query-stationary; dK/dV: key-stationary) so nothing is atomically reduced.
 #include <type_traits>
 #include "common.h"
+#include "../../include/mmdit_hip_mxpad.h"
 
 namespace {
 
@@ -469,7 +470,10 @@ __device__ __forceinline__ bf16x8 tr_frag_sw(const char* tile, int rb, int h8, i
 // MXO (fp8 inference): the output leaves as MX e4m3 -- codes in place of the bf16 rows (same (B, tokens, H * 64) geometry, one byte per
 // feature) plus E8M0 block scales in the GEMM's layout (mx_scale_index; a head's 64 features are two 32-blocks) -- so the out-projection
 // GEMM needs no quantise pass; bit-identical to the bf16 output followed by mmdit_mxfp8_quantize.
-template <int DBG = 0, bool MXO = false, int NW = 8, int NS = ANS, bool KVL = false>
+// PAD (MXO, odd H; include/mmdit_hip_mxpad.h): the code rows have pitch H * 64 + 64; the 64 pad bytes of a token (zero codes) and the scale
+// bytes of its two pad blocks (0x00) belong to no head -- the workgroups of the LAST head write them for their own query rows, so every
+// pad byte has exactly one writer in the launch.
+template <int DBG = 0, bool MXO = false, int NW = 8, int NS = ANS, bool KVL = false, bool PAD = false>
 __global__ __launch_bounds__(64 * NW) void attn_fwd_dma_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
                                                            int BH, int H, int S, int n_img, float scale,
                                                            bf16_t* __restrict__ Ox, bf16_t* __restrict__ Oc, float* __restrict__ lse,
@@ -680,9 +684,15 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_dma_kernel(const bf16_t* __r
         if (qq < S) {
           const bool img = qq < n_img;
           const int64_t tok = img ? b * n_img + qq : b * n_txt + (qq - n_img);
-          unsigned char* dst = (unsigned char*)(img ? Ox : Oc) + tok * D + h * HD + rc * 8;
+          unsigned char* dst = (unsigned char*)(img ? Ox : Oc) + tok * (D + (PAD ? 64 : 0)) + h * HD + rc * 8;
           *(uint2*)dst = make_uint2(mx_pack4(v, inv), mx_pack4(v + 4, inv));
           if ((rc & 3) == 0) (img ? scx : scc)[mx_scale_index((int)tok, h * 2 + (rc >> 2), (BH / H) * (img ? n_img : n_txt))] = (unsigned char)(ex + 127);
+          if constexpr (PAD) {
+            if (h == H - 1) {      // (workgroup-uniform) lanes rc 0-3: the token's 64 pad bytes; rc 0 / 1: the scale bytes of its two pad blocks
+              if (rc < 4) *(uint4*)((unsigned char*)(img ? Ox : Oc) + tok * (D + 64) + D + rc * 16) = make_uint4(0u, 0u, 0u, 0u);
+              if (rc < 2) (img ? scx : scc)[mx_scale_index((int)tok, H * 2 + rc, (BH / H) * (img ? n_img : n_txt))] = 0;
+            }
+          }
         }
       } else if (qq < S) {
         bf16_t* dst = qq < n_img ? Ox + ((b * n_img + qq) * (int64_t)D + h * HD) : Oc + ((b * n_txt + (qq - n_img)) * (int64_t)D + h * HD);
@@ -1080,6 +1090,20 @@ extern "C" int mmdit_attn_fwd_mx(const void* Q, const void* K, const void* V, in
   MMDIT_CHECK_ARG((Oc_fp8 && scales_c) || n_img == S);
   hipLaunchKernelGGL((attn_fwd_dma_kernel<0, true>), dim3(((S + 255) / 256) * batch * heads), dim3(512), 0, (hipStream_t)stream, (const bf16_t*)Q, (const bf16_t*)K,
                      (const bf16_t*)V, batch * heads, heads, S, n_img, scale, (bf16_t*)Ox_fp8, (bf16_t*)Oc_fp8, nullptr, (unsigned char*)scales_x, (unsigned char*)scales_c);
+  return mmdit_launch_status();
+}
+
+// include/mmdit_hip_mxpad.h: mmdit_attn_fwd_mx with the code rows zero-padded to K_pad = heads * 64 rounded up to 128 (an odd head count: the
+// PAD instantiation; an even one: the plain kernel, the same bytes as mmdit_attn_fwd_mx)
+extern "C" int mmdit_attn_fwd_mx_pad(const void* Q, const void* K, const void* V, int batch, int heads, int S, int n_img, float scale,
+                                     void* Ox_fp8, void* Oc_fp8, void* scales_x, void* scales_c, mmdit_stream_t stream) {
+  MMDIT_CHECK_ARG(Q && K && V && Ox_fp8 && scales_x && batch > 0 && heads > 0 && S > 0 && n_img > 0 && n_img <= S);
+  MMDIT_CHECK_ARG((Oc_fp8 && scales_c) || n_img == S);
+  if ((int64_t)batch * S * ((heads + 1) / 2 * 128 / 16) > 0x7fffffffll) return MMDIT_ERR_SHAPE;      // (scale rows are indexed with int)
+  if (heads % 2 == 0) return mmdit_attn_fwd_mx(Q, K, V, batch, heads, S, n_img, scale, Ox_fp8, Oc_fp8, scales_x, scales_c, stream);
+  hipLaunchKernelGGL((attn_fwd_dma_kernel<0, true, 8, ANS, false, true>), dim3(((S + 255) / 256) * batch * heads), dim3(512), 0, (hipStream_t)stream, (const bf16_t*)Q,
+                     (const bf16_t*)K, (const bf16_t*)V, batch * heads, heads, S, n_img, scale, (bf16_t*)Ox_fp8, (bf16_t*)Oc_fp8, nullptr, (unsigned char*)scales_x,
+                     (unsigned char*)scales_c);
   return mmdit_launch_status();
 }
 

@@ -35,6 +35,7 @@
 // Not tuned: no LDS-DMA ring (the tiles must pass through registers to be converted), two barriers per tile.
 #include "common.h"
 #include "../../include/mmdit_hip_ext.h"
+#include "../../include/mmdit_hip_mxpad.h"
 
 namespace {
 
@@ -84,7 +85,9 @@ __device__ __forceinline__ void map_block(int ntile, int BH, int& tile, int& bh)
 }
 
 // MXO: outputs as MX e4m3 codes + E8M0 block scales (the layout mmdit_attn_fwd_mx writes) instead of bf16 rows
-template <bool MXO>
+// PAD (MXO, odd H; include/mmdit_hip_mxpad.h): code rows of pitch H * 64 + 64; a token's 64 pad bytes (zero codes) and the scale bytes of
+// its two pad blocks (0x00) are written by the workgroups of the LAST head for their own query rows -- one writer per pad byte
+template <bool MXO, bool PAD = false>
 __global__ __launch_bounds__(NT) void attn_fwd_e4m3_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
                                                            int BH, int H, int S, int n_img, float scale,
                                                            bf16_t* __restrict__ Ox, bf16_t* __restrict__ Oc,
@@ -300,9 +303,15 @@ __global__ __launch_bounds__(NT) void attn_fwd_e4m3_kernel(const bf16_t* __restr
         float minv;
         const int ex = mx_exponent(amax, minv);
         if (qq < S) {
-          unsigned char* dst = (unsigned char*)(img ? Ox : Oc) + tok * D + h * HD + rc * 8;
+          unsigned char* dst = (unsigned char*)(img ? Ox : Oc) + tok * (D + (PAD ? 64 : 0)) + h * HD + rc * 8;
           *(uint2*)dst = make_uint2(mx_pack4(v, minv), mx_pack4(v + 4, minv));
           if ((rc & 3) == 0) (img ? scx : scc)[mx_scale_index((int)tok, h * 2 + (rc >> 2), (BH / H) * (img ? n_img : n_txt))] = (unsigned char)(ex + 127);
+          if constexpr (PAD) {
+            if (h == H - 1) {      // (workgroup-uniform) lanes rc 0-3: the token's 64 pad bytes; rc 0 / 1: the scale bytes of its two pad blocks
+              if (rc < 4) *(uint4*)((unsigned char*)(img ? Ox : Oc) + tok * (D + 64) + D + rc * 16) = make_uint4(0u, 0u, 0u, 0u);
+              if (rc < 2) (img ? scx : scc)[mx_scale_index((int)tok, H * 2 + rc, (BH / H) * (img ? n_img : n_txt))] = 0;
+            }
+          }
         }
       } else if (qq < S) {
         *(u32x4*)((img ? Ox : Oc) + tok * D + h * HD + rc * 8) = t;
@@ -322,10 +331,25 @@ extern "C" int mmdit_attn_fwd_e4m3(const void* Q, const void* K, const void* V, 
   const int64_t blocks = (int64_t)((S + QT - 1) / QT) * batch * heads;
   // (MX scale rows are indexed with int: batch * tokens of a stream must fit)
   if (blocks > 0x7fffffff || (int64_t)batch * heads > 0x7fffffff || (int64_t)batch * S > 0x7fffffff) return MMDIT_ERR_SHAPE;
-#define MMDIT_E4M3(MXO) hipLaunchKernelGGL((attn_fwd_e4m3_kernel<MXO>), dim3((unsigned)blocks), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)Q, (const bf16_t*)K, \
+#define MMDIT_E4M3(...) hipLaunchKernelGGL((attn_fwd_e4m3_kernel<__VA_ARGS__>), dim3((unsigned)blocks), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)Q, (const bf16_t*)K, \
                                            (const bf16_t*)V, batch * heads, heads, S, n_img, scale, (bf16_t*)Ox, (bf16_t*)Oc, (unsigned char*)scales_x, (unsigned char*)scales_c)
   if (scales_x) MMDIT_E4M3(true);
   else MMDIT_E4M3(false);
+  return mmdit_launch_status();
+}
+
+// include/mmdit_hip_mxpad.h: the MX-output form of mmdit_attn_fwd_e4m3 with the code rows zero-padded to K_pad = heads * 64 rounded up to 128
+// (an odd head count: the PAD instantiation; an even one: the plain launch, the same bytes)
+extern "C" int mmdit_attn_fwd_e4m3_mx_pad(const void* Q, const void* K, const void* V, int batch, int heads, int S, int n_img, float scale,
+                                          void* Ox_fp8, void* Oc_fp8, void* scales_x, void* scales_c, mmdit_stream_t stream) {
+  MMDIT_CHECK_ARG(Q && K && V && batch > 0 && heads > 0);
+  if (S < 1 || n_img < 1 || n_img > S) return MMDIT_ERR_SHAPE;
+  MMDIT_CHECK_ARG(Ox_fp8 && scales_x && ((Oc_fp8 && scales_c) || n_img == S));
+  const int64_t blocks = (int64_t)((S + QT - 1) / QT) * batch * heads;
+  if (blocks > 0x7fffffff || (int64_t)batch * S * ((heads + 1) / 2 * 128 / 16) > 0x7fffffffll) return MMDIT_ERR_SHAPE;
+  if (heads % 2 == 0) return mmdit_attn_fwd_e4m3(Q, K, V, batch, heads, S, n_img, scale, Ox_fp8, Oc_fp8, scales_x, scales_c, stream);
+  void* Ox = Ox_fp8; void* Oc = Oc_fp8;
+  MMDIT_E4M3(true, true);
 #undef MMDIT_E4M3
   return mmdit_launch_status();
 }

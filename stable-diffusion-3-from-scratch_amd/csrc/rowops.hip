@@ -5,6 +5,7 @@
 #include "qk_rows.h"
 #include "fp8_quant.h"
 #include "../../include/mmdit_hip_hd128.h"
+#include "../../include/mmdit_hip_mxpad.h"
 
 namespace {
 
@@ -22,7 +23,9 @@ __device__ __forceinline__ float bf16_round(float x) { return __builtin_bit_cast
 
 // MX (TO = unsigned char, d % 32 == 0): the normalised row leaves as e4m3 codes + E8M0 block scales (a 32-block is the 4 values of 8
 // adjacent lanes of one iteration), bit-identical to the bf16 output followed by mmdit_mxfp8_quantize.
-template <int NITX, typename TO, typename TA, bool RES, bool MX = false>
+// PAD (MX, d % 128 == 64; include/mmdit_hip_mxpad.h): the codes go to rows of pitch d + 64, the 64 bytes behind column d are zero codes and
+// the two pad blocks get the scale byte of an all-zero block -- bit-identical to the bf16 output followed by mmdit_mxfp8_quantize_pad.
+template <int NITX, typename TO, typename TA, bool RES, bool MX = false, bool PAD = false>
 __device__ __forceinline__ void ln_mod_fwd_body(int block, const float* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ shift,
                                                 int64_t ld_mod, int rows, int d, int rpb, TO* __restrict__ out,
                                                 float* __restrict__ mean_o, float* __restrict__ rstd_o,
@@ -69,6 +72,11 @@ __device__ __forceinline__ void ln_mod_fwd_body(int block, const float* __restri
   const float* sc = scale + (int64_t)b * ld_mod;
   const float* sh = shift + (int64_t)b * ld_mod;
   TO* orow = out + (int64_t)row * d;
+  const int ldo = PAD ? d + 64 : d;      // (MX: bytes per output row)
+  if constexpr (PAD) {      // lanes 0-3: the row's 64 pad bytes; lanes 0 / 1: the scale bytes of its two pad blocks
+    if (lane < 4) *(uint4*)((unsigned char*)out + (int64_t)row * ldo + d + lane * 16) = make_uint4(0u, 0u, 0u, 0u);
+    if (lane < 2) mx_scales[mx_scale_index(row, (d >> 5) + lane, rows)] = 0;
+  }
 #pragma unroll
   for (int it = 0; it < NIT; it++) {
     int ch = lane + 64 * it;
@@ -86,7 +94,7 @@ __device__ __forceinline__ void ln_mod_fwd_body(int block, const float* __restri
         amax = fmaxf(amax, __shfl_xor(amax, 4, 64));
         float inv;
         const int ex = mx_exponent(amax, inv);
-        *(unsigned*)((unsigned char*)out + (int64_t)row * d + ch * 4) = mx_pack4(o, inv);
+        *(unsigned*)((unsigned char*)out + (int64_t)row * ldo + ch * 4) = mx_pack4(o, inv);
         if ((lane & 7) == 0) mx_scales[mx_scale_index(row, ch >> 3, rows)] = (unsigned char)(ex + 127);
       } else {
         st4(orow + ch * 4, o);
@@ -104,11 +112,11 @@ struct LnFwdProb {
   const float* x; const float* scale; const float* shift; int64_t ld_mod; int rows, rpb; void* out; float* mean; float* rstd;
   const void* acc; const float* gate; int64_t ld_gate; float* xo; unsigned char* mx_scales;
 };
-template <int NIT, typename TO, typename TA, bool RES, bool MX = false>
+template <int NIT, typename TO, typename TA, bool RES, bool MX = false, bool PAD = false>
 __global__ __launch_bounds__(256) void ln_mod_fwd_kernel(LnFwdProb p0, LnFwdProb p1, int nblk0, int d) {
   const bool first = (int)blockIdx.x < nblk0;     // (workgroup-uniform)
   const LnFwdProb& p = first ? p0 : p1;
-  ln_mod_fwd_body<NIT, TO, TA, RES, MX>(first ? (int)blockIdx.x : (int)blockIdx.x - nblk0, p.x, p.scale, p.shift, p.ld_mod, p.rows, d, p.rpb, (TO*)p.out, p.mean, p.rstd,
+  ln_mod_fwd_body<NIT, TO, TA, RES, MX, PAD>(first ? (int)blockIdx.x : (int)blockIdx.x - nblk0, p.x, p.scale, p.shift, p.ld_mod, p.rows, d, p.rpb, (TO*)p.out, p.mean, p.rstd,
                                         (const TA*)p.acc, p.gate, p.ld_gate, p.xo, p.mx_scales);
 }
 
@@ -1078,8 +1086,9 @@ extern "C" int mmdit_struct_size(int which) {
 }
 extern "C" const char* mmdit_build_arch(void) { return "gfx950"; }
 
-// One launch over a list of 1 or 2 adaLN forward problems; mx_scales != NULL: the MX-emitting form (a list of one, bf16 acc).
-static int ln_mod_fwd_launch(const mmdit_ln_fwd_problem* probs, int count, int d, int out_dtype, unsigned char* mx_scales, hipStream_t s) {
+// One launch over a list of 1 or 2 adaLN forward problems; mx_scales != NULL: the MX-emitting form (bf16 acc), one scale buffer per problem;
+// pad: its zero-padded form for d % 128 == 64 (rows of pitch d + 64, include/mmdit_hip_mxpad.h).
+static int ln_mod_fwd_launch(const mmdit_ln_fwd_problem* probs, int count, int d, int out_dtype, unsigned char* const* mx_scales, hipStream_t s, bool pad = false) {
   MMDIT_CHECK_ARG(probs && count >= 1 && count <= 2 && d > 0 && d % 4 == 0 && d <= 4096);
   const bool res = probs[0].acc != nullptr;
   LnFwdProb q[2] = {};
@@ -1089,13 +1098,14 @@ static int ln_mod_fwd_launch(const mmdit_ln_fwd_problem* probs, int count, int d
     MMDIT_CHECK_ARG((p->acc != nullptr) == res);
     MMDIT_CHECK_ARG(p->x && p->scale && p->shift && p->out && p->mean && p->rstd && p->rows > 0 && p->rows_per_batch > 0 && p->ld_mod % 4 == 0);
     if (res) MMDIT_CHECK_ARG(p->gate && p->x_out && p->ld_gate % 4 == 0);
-    q[i] = LnFwdProb{p->x, p->scale, p->shift, p->ld_mod, p->rows, p->rows_per_batch, p->out, p->mean, p->rstd, p->acc, p->gate, p->ld_gate, p->x_out, mx_scales};
+    q[i] = LnFwdProb{p->x, p->scale, p->shift, p->ld_mod, p->rows, p->rows_per_batch, p->out, p->mean, p->rstd, p->acc, p->gate, p->ld_gate, p->x_out, mx_scales ? mx_scales[i] : nullptr};
     nb[i] = (p->rows + 3) / 4;
   }
   const int nit = nit_for(d);
   dim3 grid(nb[0] + nb[1]);
-#define LNL(TO, TA, RES, MX) NIT_SWITCH(nit, hipLaunchKernelGGL((ln_mod_fwd_kernel<LN_FWD_NIT, TO, TA, RES, MX>), grid, dim3(256), 0, s, q[0], q[1], nb[0], d))
-  if (mx_scales) { if (res) { LNL(unsigned char, bf16_t, true, true); } else { LNL(unsigned char, bf16_t, false, true); } }
+#define LNL(TO, TA, RES, ...) NIT_SWITCH(nit, hipLaunchKernelGGL((ln_mod_fwd_kernel<LN_FWD_NIT, TO, TA, RES, __VA_ARGS__>), grid, dim3(256), 0, s, q[0], q[1], nb[0], d))
+  if (mx_scales && pad) { if (res) { LNL(unsigned char, bf16_t, true, true, true); } else { LNL(unsigned char, bf16_t, false, true, true); } }
+  else if (mx_scales) { if (res) { LNL(unsigned char, bf16_t, true, true); } else { LNL(unsigned char, bf16_t, false, true); } }
   else if (out_dtype == MMDIT_BF16) { if (res) { LNL(bf16_t, bf16_t, true, false); } else { LNL(bf16_t, bf16_t, false, false); } }
   else if (out_dtype == MMDIT_F32) { if (res) { LNL(float, float, true, false); } else { LNL(float, float, false, false); } }
   else return MMDIT_ERR_DTYPE;
@@ -1113,7 +1123,20 @@ extern "C" int mmdit_ln_modulate_fwd_mx(const float* x, const void* acc, int acc
                                         void* q_fp8, void* scales_e8m0, float* mean, float* rstd, mmdit_stream_t stream) {
   MMDIT_CHECK_ARG(scales_e8m0 && d % 64 == 0 && (!acc || acc_dtype == MMDIT_BF16));
   const mmdit_ln_fwd_problem p = {x, acc, gate, ld_gate, x_out, scale, shift, ld_mod, rows, rpb, q_fp8, mean, rstd};
-  return ln_mod_fwd_launch(&p, 1, d, MMDIT_FP8, (unsigned char*)scales_e8m0, (hipStream_t)stream);
+  unsigned char* const sc[1] = {(unsigned char*)scales_e8m0};
+  return ln_mod_fwd_launch(&p, 1, d, MMDIT_FP8, sc, (hipStream_t)stream);
+}
+
+// include/mmdit_hip_mxpad.h: the MX-emitting adaLN over a list of 1 or 2 problems, the codes in rows of K_pad = d rounded up to 128
+extern "C" int mmdit_ln_modulate_fwd_mx_pad(const mmdit_ln_fwd_problem* probs, int count, int d, int acc_dtype, void* scales_e8m0_0, void* scales_e8m0_1,
+                                            mmdit_stream_t stream) {
+  MMDIT_CHECK_ARG(probs && count >= 1 && count <= 2 && scales_e8m0_0 && (count == 1 || scales_e8m0_1));
+  if (d <= 0 || d % 64 != 0) return MMDIT_ERR_SHAPE;
+  for (int i = 0; i < count; i++)      // (the rest of a problem is checked by the launch; the row index of a scale byte is an int)
+    if (probs[i].rows > 0 && (int64_t)probs[i].rows * ((d + 127) / 128 * 128) / 16 > 0x7fffffffll) return MMDIT_ERR_SHAPE;
+  MMDIT_CHECK_ARG(!probs[0].acc || acc_dtype == MMDIT_BF16);      // (as mmdit_ln_modulate_fwd_mx)
+  unsigned char* const sc[2] = {(unsigned char*)scales_e8m0_0, (unsigned char*)scales_e8m0_1};
+  return ln_mod_fwd_launch(probs, count, d, MMDIT_FP8, sc, (hipStream_t)stream, d % 128 != 0);
 }
 
 extern "C" int mmdit_gate_residual_fwd(const float* x, const void* acc, int acc_dtype, const float* gate, int64_t ld_gate, int rows, int d, int rpb,

@@ -71,7 +71,8 @@ def _to_fp8(m, p):
     into rows zero-padded to ops.fp8_k_pad(K), the next multiple of the e4m3 kernels' 128-wide K tile, and the GEMM runs on that K -- a zero
     code times anything is zero, the product is exact.  Only problems whose K is no multiple of 64 stay bf16."""
     A, B = p["A"], p["B"]
-    pre = isinstance(A, ops.MxAct)       # the producer already emitted MX e4m3 (block_fwd checked the site's eligibility)
+    pre = isinstance(A, ops.MxAct)       # the producer already emitted MX e4m3 (block_fwd checked the site's eligibility): K wide, or -- K % 128 == 64,
+                                         # the producers' pad=True forms -- already ops.fp8_k_pad(K) wide like the cached padded weight copy below
     if not pre and (A.dtype != BF16 or B.dtype != BF16 or ops.fp8_k_pad(A.shape[1]) is None or p.get("a_kmajor") or p.get("b_kmajor")):
         return p
     ent, gen = m._q.get(id(B)), getattr(B, "_mmdit_gen", 0)     # (the bf16 copy is refreshed in place: packing.Pack.generation)
@@ -291,7 +292,7 @@ def _norm(m, P, scale, shift, rpb, mx=False):
     leave as MX e4m3 (ops.MxAct) for the fp8 GEMM that consumes them."""
     pend = isinstance(P, Pending) and P.acc is not None
     if mx:
-        return ops.ln_modulate_fwd_mx(P.x if isinstance(P, Pending) else P, scale, shift, rpb, acc=P.acc if pend else None, gate=P.gate if pend else None)
+        return ops.ln_modulate_fwd_mx(P.x if isinstance(P, Pending) else P, scale, shift, rpb, acc=P.acc if pend else None, gate=P.gate if pend else None, pad=True)
     if pend:
         return ops.ln_modulate_fwd_res(P.x, P.acc, P.gate, scale, shift, rpb, m.T)
     x = P.x if isinstance(P, Pending) else P
@@ -302,8 +303,10 @@ def _norm_pair(m, a, b, mx=False):
     """adaLN of the image stream (a) and of the text stream (b) = (P, scale, shift, rpb) each: ONE launch when both are plain or both
     carry a pending gated residual update (ops.ln_modulate_fwd_pair; ~5 us less per pair than two launches), two launches otherwise."""
     pend = [isinstance(P, Pending) and P.acc is not None for P, *_ in (a, b)]
-    dev = (a[0].x if isinstance(a[0], Pending) else a[0]).device
-    if mx or pend[0] != pend[1] or dev.type != "cuda" or not _LN_PAIR:
+    x0 = a[0].x if isinstance(a[0], Pending) else a[0]
+    dev = x0.device
+    # MX outputs: the list launch exists in the zero-padded form only (d % 128 == 64, ops._ln_fwd); d % 128 == 0 keeps its two launches
+    if (mx and not mx_fuse_padded(x0.shape[1])) or pend[0] != pend[1] or dev.type != "cuda" or not _LN_PAIR:
         return _norm(m, *a, mx=mx), _norm(m, *b, mx=mx)
     args = []
     for (P, scale, shift, rpb), pe in zip((a, b), pend):
@@ -311,7 +314,7 @@ def _norm_pair(m, a, b, mx=False):
         if pe:
             d.update(acc=P.acc, gate=P.gate)
         args.append(d)
-    ra, rb = ops.ln_modulate_fwd_pair(args[0], args[1], m.T)
+    ra, rb = ops.ln_modulate_fwd_pair(args[0], args[1], m.T, mx=mx, pad=mx)
     return ra, rb
 
 
@@ -322,6 +325,17 @@ def _ln_bwd_pair(a, b):
     if ga != gb or not a["x"].is_cuda or not _LN_PAIR:
         return [ops.ln_modulate_bwd(p["dout"], p["x"], p["mean"], p["rstd"], p["scale"], p["dres"], p["rpb"], p["dscale"], p["dshift"], gated=p.get("gated")) for p in (a, b)]
     return ops.ln_modulate_bwd_pair(a, b)
+
+
+def mx_fuse_width(d):
+    """Width rule of the producer-fused e4m3 routes of a block (MX-emitting adaLN / attention, SwiGLU in the up-projection's epilogue): every d
+    an e4m3 GEMM operand can be made from (ops.fp8_k_pad) -- d % 128 == 0 as it is, d % 128 == 64 zero-padded to the next multiple of 128."""
+    return ops.fp8_k_pad(d) is not None
+
+
+def mx_fuse_padded(d):
+    """True when the fused route of mx_fuse_width(d) runs on zero-padded rows."""
+    return mx_fuse_width(d) and ops.fp8_k_pad(d) != d
 
 
 def block_fwd(m, w, X, C, y, dims, rope, cond=None, keep=True, lazy=False):
@@ -357,8 +371,9 @@ def block_fwd(m, w, X, C, y, dims, rope, cond=None, keep=True, lazy=False):
         sv.mod = _gemm(m, sv.yp, w.Wmod, out_dtype=F32)
     ms = _mod_views(sv.mod, d, w.last)
     # "mxfp8" inference: the activations that feed the four fp8 GEMM sites leave their producers (adaLN, attention, SwiGLU) as MX e4m3
-    # -- no quantise passes -- when every site of the block is eligible (K % 128; SwiGLU MLPs)
-    mxf = (m.mx and not keep and dev.type == "cuda" and d % 128 == 0 and not w.mlp_x.gelu
+    # -- no quantise passes -- when every site of the block is eligible (SwiGLU MLPs; K = d a multiple of 64: at d % 128 == 64 the producers
+    # write rows zero-padded to ops.fp8_k_pad(d), include/mmdit_hip_mxpad.h; hidden % 128)
+    mxf = (m.mx and not keep and dev.type == "cuda" and mx_fuse_width(d) and not w.mlp_x.gelu
            and w.mlp_x.hidden % 128 == 0 and (w.last or (not w.mlp_c.gelu and w.mlp_c.hidden % 128 == 0)) and _MX_FUSE)
 
     (sv.X, sv.ln1x, sv.mu1x, sv.rs1x), (sv.C, sv.ln1c, sv.mu1c, sv.rs1c) = _norm_pair(m, (X, ms.scale1x, ms.shift1x, N), (C, ms.scale1c, ms.shift1c, Mt), mx=mxf)
@@ -422,7 +437,7 @@ def block_fwd(m, w, X, C, y, dims, rope, cond=None, keep=True, lazy=False):
         if both:
             sv.Oca = m.act(sv.Oc.view(B * Mt, d))
     elif mxf:
-        sv.Oxa, sv.Oca = ops.attn_fwd_e4m3(sv.Q, sv.K, sv.V, N, 64 ** -0.5, mx=True) if m.attn_e4m3 else ops.attn_fwd_mx(sv.Q, sv.K, sv.V, N, 64 ** -0.5)
+        sv.Oxa, sv.Oca = ops.attn_fwd_e4m3_mx(sv.Q, sv.K, sv.V, N, 64 ** -0.5, pad=True) if m.attn_e4m3 else ops.attn_fwd_mx(sv.Q, sv.K, sv.V, N, 64 ** -0.5, pad=True)
     elif m.fp8 and m.attn_e4m3 and not keep and not merge and dev.type == "cuda":      # (inference: no lse)
         sv.Ox, sv.Oc = ops.attn_fwd_e4m3(sv.Q, sv.K, sv.V, N, 64 ** -0.5)
         sv.Oxa = sv.Ox.view(B * N, d)
@@ -447,9 +462,9 @@ def block_fwd(m, w, X, C, y, dims, rope, cond=None, keep=True, lazy=False):
     else:
         sv.C1 = sv.C
         sv.X1, sv.ln2x, sv.mu2x, sv.rs2x = _norm(m, Pending(sv.X, sv.acc_ox, ms.gate1x, N), ms.scale2x, ms.shift2x, N, mx=mxf)
-    # SwiGLU in the up-projection's epilogue (bf16 mode, hidden % 128 == 0, K % 64 == 0): the GEMM writes the pre-activations and
-    # the activation; otherwise (GELU, parity / fp8 mode, odd sizes) the activation is a row kernel over the GEMM output
-    fuse = _FUSE_SWIGLU and m.fast and dev.type == "cuda" and not w.mlp_x.gelu and w.mlp_x.hidden % 128 == 0 and d % (128 if m.fp8 else 64) == 0
+    # SwiGLU in the up-projection's epilogue (hidden % 128 == 0, K % 64 == 0; fp8 / mxfp8: the e4m3 GEMM runs on ops.fp8_k_pad(K)): the GEMM
+    # writes the pre-activations and the activation; otherwise (GELU, parity mode, odd sizes) the activation is a row kernel over the GEMM output
+    fuse = _FUSE_SWIGLU and m.fast and dev.type == "cuda" and not w.mlp_x.gelu and w.mlp_x.hidden % 128 == 0 and (mx_fuse_width(d) if m.fp8 else d % 64 == 0)
 
     def up(xn, mw, rows):
         if fuse and mxf:     # MX in, MX out: the activation leaves the epilogue as e4m3 codes + block scales (no quantise pass before w3)

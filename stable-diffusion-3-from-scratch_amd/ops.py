@@ -390,9 +390,17 @@ def _mx_buffers(rows, K, device):
     return (torch.empty((rows, K), dtype=torch.float8_e4m3fn, device=device), torch.empty(mx_scale_bytes(rows, K), dtype=torch.uint8, device=device))
 
 
-def ln_modulate_fwd_mx(x, scale, shift, rows_per_batch, acc=None, gate=None):
+def ln_modulate_fwd_mx(x, scale, shift, rows_per_batch, acc=None, gate=None, pad=False):
     """adaLN with the output in MX e4m3 (mmdit_ln_modulate_fwd_mx); acc / gate: the pending gated residual update, as in
-    ln_modulate_fwd_res.  Returns (x1 fp32 (x itself without acc), MxAct, mean, rstd)."""
+    ln_modulate_fwd_res.  Returns (x1 fp32 (x itself without acc), MxAct, mean, rstd).
+    pad=True: d % 128 == 64 gives an MxAct (rows, fp8_k_pad(d)) with zero codes behind column d and the scales of a (rows, fp8_k_pad(d))
+    operand (mmdit_ln_modulate_fwd_mx_pad, include/mmdit_hip_mxpad.h): what quant_mxfp8(pad=True) makes of the bf16 output; every other d
+    as without it."""
+    if _pads(x, pad):
+        p = dict(x=x, scale=scale, shift=shift, rpb=rows_per_batch)
+        if acc is not None:
+            p.update(acc=acc, gate=gate)
+        return _ln_fwd([p], None, mx=True, pad=True)[0]
     rows, d = x.shape
     q, sc = _mx_buffers(rows, d, x.device)
     mean = torch.empty((rows,), dtype=torch.float32, device=x.device)
@@ -412,20 +420,26 @@ def swiglu_fwd_mx(gu, hidden):
     return MxAct(q, sc)
 
 
-def attn_fwd_mx(Q, K, V, n_img, scale):
-    """Flash attention forward with the head-merged outputs in MX e4m3 (mmdit_attn_fwd_mx): returns (MxAct (B*N, H*64), MxAct (B*M, H*64) or None)."""
+def attn_fwd_mx(Q, K, V, n_img, scale, pad=False):
+    """Flash attention forward with the head-merged outputs in MX e4m3 (mmdit_attn_fwd_mx): returns (MxAct (B*N, H*64), MxAct (B*M, H*64) or None).
+    pad=True: an odd head count (H * 64 = 64 mod 128) gives MxActs fp8_k_pad(H * 64) wide, zero codes behind column H * 64 and the scales of
+    an operand of that width (mmdit_attn_fwd_mx_pad, include/mmdit_hip_mxpad.h); every other call as without it."""
     B, H, S, hd = Q.shape
     n_txt = S - n_img
+    if pad and (H * hd) % 128 == 64:
+        Dp = fp8_k_pad(H * hd)
+        qx, sx = _mx_buffers(B * n_img, Dp, Q.device)
+        qc, scc = _mx_buffers(B * n_txt, Dp, Q.device) if n_txt else (None, None)
+        check(_lib.lib().mmdit_attn_fwd_mx_pad(_p(Q), _p(K), _p(V), B, H, S, n_img, float(scale), _p(qx), _p(qc), _p(sx), _p(scc), _s()), "mmdit_attn_fwd_mx_pad")
+        return MxAct(qx, sx), (MxAct(qc, scc) if n_txt else None)
     qx, sx = _mx_buffers(B * n_img, H * hd, Q.device)
     qc, scc = _mx_buffers(B * n_txt, H * hd, Q.device) if n_txt else (None, None)
     check(_lib.lib().mmdit_attn_fwd_mx(_p(Q), _p(K), _p(V), B, H, S, n_img, float(scale), _p(qx), _p(qc), _p(sx), _p(scc), _s()), "mmdit_attn_fwd_mx")
     return MxAct(qx, sx), (MxAct(qc, scc) if n_txt else None)
 
 
-def attn_fwd_e4m3(Q, K, V, n_img, scale, mx=False):
-    """Flash attention forward with e4m3 operands on both matrix products (mmdit_attn_fwd_e4m3, include/mmdit_hip_ext.h; inference, no lse).
-    Q, K, V: bf16 (B, H, S, 64), quantised inside the launch.  Returns the head-merged (Ox (B, N, H*64), Oc (B, M, H*64) or None) in bf16, or
-    with mx=True what attn_fwd_mx returns: (MxAct (B*N, H*64), MxAct (B*M, H*64) or None)."""
+def _attn_e4m3_operands(Q, K, V, n_img):
+    """Operand checks of the e4m3 attention launches; returns (B, H, S, tokens of the text stream, H * 64)."""
     B, H, S, hd = Q.shape
     if hd != 64:
         raise RuntimeError("attention kernels are built for head_dim 64 (the reference's dim = 64*num_heads convention)")
@@ -435,9 +449,16 @@ def attn_fwd_e4m3(Q, K, V, n_img, scale, mx=False):
         if t.dtype != torch.bfloat16:
             raise RuntimeError("attention operands are bfloat16")
         _c(t)
-    n_txt, D = S - n_img, H * hd
     if S < 1 or not 0 <= n_img <= S:
         check(_lib.ERR_SHAPE, "mmdit_attn_fwd_e4m3")       # (the library's own answer, before a buffer of negative size is asked for)
+    return B, H, S, S - n_img, H * hd
+
+
+def attn_fwd_e4m3(Q, K, V, n_img, scale, mx=False):
+    """Flash attention forward with e4m3 operands on both matrix products (mmdit_attn_fwd_e4m3, include/mmdit_hip_ext.h; inference, no lse).
+    Q, K, V: bf16 (B, H, S, 64), quantised inside the launch.  Returns the head-merged (Ox (B, N, H*64), Oc (B, M, H*64) or None) in bf16, or
+    with mx=True what attn_fwd_mx returns: (MxAct (B*N, H*64), MxAct (B*M, H*64) or None)."""
+    B, H, S, n_txt, D = _attn_e4m3_operands(Q, K, V, n_img)
     if mx:
         qx, sx = _mx_buffers(B * n_img, D, Q.device)
         qc, scc = _mx_buffers(B * n_txt, D, Q.device) if n_txt else (None, None)
@@ -447,6 +468,19 @@ def attn_fwd_e4m3(Q, K, V, n_img, scale, mx=False):
     Oc = torch.empty((B, n_txt, D), dtype=torch.bfloat16, device=Q.device) if n_txt else None
     check(_lib.lib().mmdit_attn_fwd_e4m3(_p(Q), _p(K), _p(V), B, H, S, n_img, float(scale), _p(Ox), _p(Oc), None, None, _s()), "mmdit_attn_fwd_e4m3")
     return Ox, Oc
+
+
+def attn_fwd_e4m3_mx(Q, K, V, n_img, scale, pad=False):
+    """attn_fwd_e4m3 with MX outputs.  pad=True: an odd head count (H * 64 = 64 mod 128) gives MxActs fp8_k_pad(H * 64) wide, zero codes behind
+    column H * 64 and the scales of an operand of that width, as attn_fwd_mx(pad=True) does it (mmdit_attn_fwd_e4m3_mx_pad,
+    include/mmdit_hip_mxpad.h); every other call is attn_fwd_e4m3(mx=True).  (A function of its own: attn_fwd_e4m3's argument list is pinned.)"""
+    B, H, S, n_txt, D = _attn_e4m3_operands(Q, K, V, n_img)
+    if not (pad and D % 128 == 64):
+        return attn_fwd_e4m3(Q, K, V, n_img, scale, mx=True)
+    qx, sx = _mx_buffers(B * n_img, fp8_k_pad(D), Q.device)
+    qc, scc = _mx_buffers(B * n_txt, fp8_k_pad(D), Q.device) if n_txt else (None, None)
+    check(_lib.lib().mmdit_attn_fwd_e4m3_mx_pad(_p(Q), _p(K), _p(V), B, H, S, n_img, float(scale), _p(qx), _p(qc), _p(sx), _p(scc), _s()), "mmdit_attn_fwd_e4m3_mx_pad")
+    return MxAct(qx, sx), (MxAct(qc, scc) if n_txt else None)
 
 
 def quant_mxfp8(x, pad=False):
@@ -525,29 +559,38 @@ def cast_multi(pairs):
     check(_lib.lib().mmdit_cast_multi(_p(t["dev"][0]), _p(t["dev"][1]), _p(t["dev"][2]), t["n"], _s()), "mmdit_cast_multi")
 
 
-def _ln_fwd(plist, out_dtype):
+def _ln_fwd(plist, out_dtype, mx=False, pad=False):
     """adaLN forward of a list of 1 or 2 problems of the same width in ONE launch (mmdit_ln_modulate_fwd).  A problem is a dict with x, scale,
     shift, rpb and -- in all problems or in none -- acc, gate (the pending gated residual update x1 = x + gate[b] * acc).
-    Returns [(x1, out, mean, rstd)] per problem (x1 is x itself without acc)."""
+    Returns [(x1, out, mean, rstd)] per problem (x1 is x itself without acc).
+    mx=True (out_dtype unused, bf16 acc): out is an MxAct, the list form of ln_modulate_fwd_mx on mmdit_ln_modulate_fwd_mx_pad
+    (include/mmdit_hip_mxpad.h) -- with pad=True and d % 128 == 64 fp8_k_pad(d) wide with zero codes behind column d; d % 128 == 0 as
+    ln_modulate_fwd_mx writes it.  d % 128 == 64 without pad is the single-problem launch's (ln_modulate_fwd_mx)."""
     res = plist[0].get("acc") is not None
     d = plist[0]["x"].shape[1]
+    if mx and d % 128 and not (pad and d % 128 == 64):
+        raise RuntimeError(f"adaLN with MX output over a problem list: d = {d} needs pad=True and d % 64 == 0 (the e4m3 GEMM's 128-wide K tile)")
     probs, outs, keep = (_lib.LnFwdProblem * len(plist))(), [], []
     for q, p in zip(probs, plist):
         assert (p.get("acc") is not None) == res
         x = _c(p["x"])
         rows, dev = x.shape[0], x.device
         x1 = torch.empty((rows, d), dtype=torch.float32, device=dev) if res else x
-        out = torch.empty((rows, d), dtype=out_dtype, device=dev)
+        out = MxAct(*_mx_buffers(rows, fp8_k_pad(d), dev)) if mx else torch.empty((rows, d), dtype=out_dtype, device=dev)
         mean = torch.empty((rows,), dtype=torch.float32, device=dev)
         rstd = torch.empty((rows,), dtype=torch.float32, device=dev)
         q.x, q.scale, q.shift, q.ld_mod, q.rows, q.rows_per_batch = _p(x), _p(p["scale"]), _p(p["shift"]), p["scale"].stride(0), rows, p["rpb"]
-        q.out, q.mean, q.rstd = _p(out), _p(mean), _p(rstd)
+        q.out, q.mean, q.rstd = _p(out.q if mx else out), _p(mean), _p(rstd)
         keep.append(x)
         if res:
             acc = _c(p["acc"])
             q.acc, q.gate, q.ld_gate, q.x_out = _p(acc), _p(p["gate"]), p["gate"].stride(0), _p(x1)
             keep.append(acc)
         outs.append((x1, out, mean, rstd))
+    if mx:
+        check(_lib.lib().mmdit_ln_modulate_fwd_mx_pad(probs, len(plist), d, _dt(plist[0]["acc"]) if res else BF16, _p(outs[0][1].sc), _p(outs[-1][1].sc) if len(outs) > 1 else None,
+                                                      _s()), "mmdit_ln_modulate_fwd_mx_pad")
+        return outs
     acc_dt = _dt(plist[0]["acc"]) if res else _DT[out_dtype]
     check(_lib.lib().mmdit_ln_modulate_fwd(probs, len(plist), d, acc_dt, _DT[out_dtype], _s()), "mmdit_ln_modulate_fwd")
     return outs
@@ -562,10 +605,10 @@ def ln_modulate_fwd_res(x, acc, gate, scale, shift, rows_per_batch, out_dtype):
     return _ln_fwd([dict(x=x, scale=scale, shift=shift, rpb=rows_per_batch, acc=acc, gate=gate)], out_dtype)[0]
 
 
-def ln_modulate_fwd_pair(pa, pb, out_dtype):
+def ln_modulate_fwd_pair(pa, pb, out_dtype, mx=False, pad=False):
     """Two adaLN forward problems of the same width in ONE launch (the image and the text stream of a block).  pa / pb: dicts as for
-    _ln_fwd.  Returns [(x1, out, mean, rstd), (x1, out, mean, rstd)]."""
-    return _ln_fwd([pa, pb], out_dtype)
+    _ln_fwd.  Returns [(x1, out, mean, rstd), (x1, out, mean, rstd)]; mx / pad: the outputs as MxActs, see _ln_fwd."""
+    return _ln_fwd([pa, pb], out_dtype, mx=mx, pad=pad)
 
 
 def _ln_bwd(plist):
