@@ -24,6 +24,7 @@ HEADER_TEXTLOSS_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_textloss.
 HEADER_COS2_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_cos2.h")   # the attn_type="cosine2" entry points, outside it as well
 HEADER_FP8PAD_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_fp8pad.h")   # the zero-padded e4m3 quantisers, outside it as well
 HEADER_MXPAD_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_mxpad.h")   # the MX producers on zero-padded rows, outside it as well
+HEADER_OPTIM_PATH = os.path.join(_HERE, "..", "include", "mmdit_hip_optim.h")   # the AdamW update with per-tensor step counters, outside it as well
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_SILU, ACT_SWIGLU, ACT_SWIGLU_BWD = 0, 1, 2, 3
@@ -202,6 +203,10 @@ _MXPAD_SIGNATURES = {
     "mmdit_attn_fwd_mx_pad": _SIGNATURES["mmdit_attn_fwd_mx"],
     "mmdit_attn_fwd_e4m3_mx_pad": _EXT_SIGNATURES["mmdit_attn_fwd_e4m3"],
 }
+# entry points of include/mmdit_hip_optim.h (the AdamW update reading one step counter per tensor; otherwise the argument list of mmdit_adamw_step_dlr)
+_OPTIM_SIGNATURES = {
+    "mmdit_adamw_step_dlr_pt": _SIGNATURES["mmdit_adamw_step_dlr"],
+}
 COS2_HEAD_DIM = 64                                     # MMDIT_COS2_HEAD_DIM
 ATTN_COS2_TOKEN_CHUNK, ATTN_COS2_ROW_TILE = 128, 64    # MMDIT_ATTN_COS2_TOKEN_CHUNK / MMDIT_ATTN_COS2_ROW_TILE
 HEAD_DIMS = (64, 128)                                  # head widths the attention and QK-norm / RoPE kernels are built for
@@ -277,6 +282,13 @@ def declared_mxpad_symbols():
     return sorted(set(re.findall(r"\b(mmdit_[a-z0-9_]+)\s*\(", txt)) - {"mmdit_stream_t"})
 
 
+def declared_optim_symbols():
+    """Entry points declared by include/mmdit_hip_optim.h (parsed the same way)."""
+    with open(HEADER_OPTIM_PATH) as f:
+        txt = f.read()
+    return sorted(set(re.findall(r"\b(mmdit_[a-z0-9_]+)\s*\(", txt)) - {"mmdit_stream_t"})
+
+
 def lib():
     """Load the HIP library (once).  Raises RuntimeError if it is not built."""
     global _lib
@@ -295,7 +307,8 @@ def lib():
             pass
         L = ctypes.CDLL(LIB_PATH)
         for name, (argtypes, restype) in (list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_HD128_SIGNATURES.items()) + list(_ROPE3_SIGNATURES.items())
-                                          + list(_QKHALF_SIGNATURES.items()) + list(_TEXTLOSS_SIGNATURES.items()) + list(_COS2_SIGNATURES.items()) + list(_FP8PAD_SIGNATURES.items()) + list(_MXPAD_SIGNATURES.items())):
+                                          + list(_QKHALF_SIGNATURES.items()) + list(_TEXTLOSS_SIGNATURES.items()) + list(_COS2_SIGNATURES.items()) + list(_FP8PAD_SIGNATURES.items()) + list(_MXPAD_SIGNATURES.items())
+                                          + list(_OPTIM_SIGNATURES.items())):
             fn = getattr(L, name)  # AttributeError -> symbol missing: fail loudly
             fn.argtypes = argtypes
             fn.restype = restype

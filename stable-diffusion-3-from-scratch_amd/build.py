@@ -22,6 +22,7 @@ HEADER_TEXTLOSS = os.path.join(HERE, "..", "include", "mmdit_hip_textloss.h")  #
 HEADER_COS2 = os.path.join(HERE, "..", "include", "mmdit_hip_cos2.h")  # the attn_type="cosine2" entry points, outside it as well
 HEADER_FP8PAD = os.path.join(HERE, "..", "include", "mmdit_hip_fp8pad.h")  # the zero-padded e4m3 quantisers, outside it as well
 HEADER_MXPAD = os.path.join(HERE, "..", "include", "mmdit_hip_mxpad.h")  # the MX producers on zero-padded rows (rowops.hip, attention.hip, attention_e4m3.hip), outside it as well
+HEADER_OPTIM = os.path.join(HERE, "..", "include", "mmdit_hip_optim.h")  # the AdamW update with per-tensor step counters (optim.hip), outside it as well
 SOURCES = ["gemm.hip", "gemm_dma.hip", "gemm_lean.hip", "gemm8p.hip", "gemm8p_inf.hip", "rowops.hip", "fp8_pad.hip", "attention.hip", "attention_e4m3.hip", "attention_hd128.hip", "rowops_rope3.hip", "attention_qkhalf.hip", "rowops_qkhalf.hip", "attention_cos2.hip", "rowops_cos2.hip", "text_loss.hip", "vae.hip", "vae_attn.hip", "optim.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + os.environ.get("MMDIT_EXTRA_HIPCC_FLAGS", "").split()
@@ -48,7 +49,7 @@ def _read(path):
 
 def source_hash(src):
     """Content hash of everything object `src` depends on."""
-    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [HEADER, HEADER_EXT, HEADER_HD128, HEADER_ROPE3, HEADER_QKHALF, HEADER_TEXTLOSS, HEADER_COS2, HEADER_FP8PAD, HEADER_MXPAD]
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [HEADER, HEADER_EXT, HEADER_HD128, HEADER_ROPE3, HEADER_QKHALF, HEADER_TEXTLOSS, HEADER_COS2, HEADER_FP8PAD, HEADER_MXPAD, HEADER_OPTIM]
     if src == "gemm8p_inf.hip":
         headers.append(os.path.join(CSRC, "gemm8p.hip"))      # (it is that file, compiled with MMDIT_G8_PART 2)
     return _sha([os.path.join(CSRC, src)] + headers, " ".join([HIPCC] + FLAGS + SOURCE_FLAGS.get(src, [])))

@@ -9,9 +9,12 @@
 #include "common.h"
 
 #include "../../include/mmdit_hip.h"
+#include "../../include/mmdit_hip_optim.h"
 
 namespace {
 
+// (the chunk map, the alignment tests of the vector paths, the 2 * TPB double-buffered loops and the n % 4 / n % 8 tails below are RESTATED in
+// tests/test_optim_edges_gpu.py -- chunk_map / adamw_path / sumsq_path / cast_path; a change here must be made there as well)
 constexpr int CHUNK = MMDIT_ADAMW_CHUNK, TPB = 256;
 
 __device__ __forceinline__ float block_sum(float v, float* red) {
@@ -87,6 +90,7 @@ struct AdamConst {
   float eps;
   double lr, b1d, b2d, wd;
   const double* lr_dev;   // not NULL: the learning rate is read from device memory (a captured launch must not bake it in)
+  int per_tensor;         // 1: step_count is an array with one counter per row of the tensor table (mmdit_adamw_step_dlr_pt), 0: one scalar for the launch
 };
 
 __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const AdamConst& k, float step_size, float bc2_sqrt) {
@@ -111,15 +115,16 @@ __global__ __launch_bounds__(TPB) void adamw_kernel(const mmdit_adamw_tensor* __
     if (coef_found[1] != 0.f) return;   // inf/nan gradients: the whole step is skipped (GradScaler.step)
     coef = coef_found[0];
   }
-  const double step = (double)step_count[0] + 1.0;
+  const int c = blockIdx.x;
+  const int ti = chunk_tensor[c];
+  const double step = (double)step_count[k.per_tensor ? ti : 0] + 1.0;
   if (k.lr_dev) {
     k.lr = k.lr_dev[0];
     k.decay = (float)(1.0 - k.lr * k.wd);
   }
   const float step_size = (float)(k.lr / (1.0 - pow(k.b1d, step)));
   const float bc2_sqrt = (float)sqrt(1.0 - pow(k.b2d, step));
-  const int c = blockIdx.x;
-  const mmdit_adamw_tensor t = tensors[chunk_tensor[c]];
+  const mmdit_adamw_tensor t = tensors[ti];
   const int64_t off = chunk_off[c];
   const int n = (int)min((int64_t)CHUNK, t.numel - off);
   float* P = t.param + off;
@@ -213,13 +218,13 @@ extern "C" int mmdit_adamw_step(const mmdit_adamw_tensor* tensors, const int* ch
   k.b2 = (float)beta2;
   k.one_m_b2 = (float)(1.0 - beta2);
   k.eps = (float)eps;
-  k.lr = lr; k.b1d = beta1; k.b2d = beta2; k.wd = weight_decay; k.lr_dev = nullptr;
+  k.lr = lr; k.b1d = beta1; k.b2d = beta2; k.wd = weight_decay; k.lr_dev = nullptr; k.per_tensor = 0;
   hipLaunchKernelGGL(adamw_kernel, dim3(n_chunks), dim3(TPB), 0, (hipStream_t)stream, tensors, chunk_tensor, chunk_off, coef_found, step_count, k);
   return mmdit_launch_status();
 }
 
-extern "C" int mmdit_adamw_step_dlr(const mmdit_adamw_tensor* tensors, const int* chunk_tensor, const int64_t* chunk_off, int n_chunks, const float* coef_found,
-                                    const float* step_count, const double* lr_dev, double beta1, double beta2, double eps, double weight_decay, mmdit_stream_t stream) {
+static int adamw_dlr_launch(const mmdit_adamw_tensor* tensors, const int* chunk_tensor, const int64_t* chunk_off, int n_chunks, const float* coef_found,
+                            const float* step_count, int per_tensor, const double* lr_dev, double beta1, double beta2, double eps, double weight_decay, mmdit_stream_t stream) {
   MMDIT_CHECK_ARG(tensors && chunk_tensor && chunk_off && step_count && lr_dev && n_chunks > 0);
   MMDIT_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && weight_decay >= 0.0);
   AdamConst k;
@@ -228,7 +233,18 @@ extern "C" int mmdit_adamw_step_dlr(const mmdit_adamw_tensor* tensors, const int
   k.b2 = (float)beta2;
   k.one_m_b2 = (float)(1.0 - beta2);
   k.eps = (float)eps;
-  k.lr = 0.0; k.b1d = beta1; k.b2d = beta2; k.wd = weight_decay; k.lr_dev = lr_dev;
+  k.lr = 0.0; k.b1d = beta1; k.b2d = beta2; k.wd = weight_decay; k.lr_dev = lr_dev; k.per_tensor = per_tensor;
   hipLaunchKernelGGL(adamw_kernel, dim3(n_chunks), dim3(TPB), 0, (hipStream_t)stream, tensors, chunk_tensor, chunk_off, coef_found, step_count, k);
   return mmdit_launch_status();
+}
+
+extern "C" int mmdit_adamw_step_dlr(const mmdit_adamw_tensor* tensors, const int* chunk_tensor, const int64_t* chunk_off, int n_chunks, const float* coef_found,
+                                    const float* step_count, const double* lr_dev, double beta1, double beta2, double eps, double weight_decay, mmdit_stream_t stream) {
+  return adamw_dlr_launch(tensors, chunk_tensor, chunk_off, n_chunks, coef_found, step_count, 0, lr_dev, beta1, beta2, eps, weight_decay, stream);
+}
+
+// include/mmdit_hip_optim.h: the same launch with one step counter PER TENSOR (step_counts[i] belongs to tensors[i]), as torch's fused AdamW keeps them
+extern "C" int mmdit_adamw_step_dlr_pt(const mmdit_adamw_tensor* tensors, const int* chunk_tensor, const int64_t* chunk_off, int n_chunks, const float* coef_found,
+                                       const float* step_counts, const double* lr_dev, double beta1, double beta2, double eps, double weight_decay, mmdit_stream_t stream) {
+  return adamw_dlr_launch(tensors, chunk_tensor, chunk_off, n_chunks, coef_found, step_counts, 1, lr_dev, beta1, beta2, eps, weight_decay, stream);
 }

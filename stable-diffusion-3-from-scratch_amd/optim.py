@@ -3,7 +3,9 @@ parameter list (csrc/optim.hip, include/mmdit_hip.h `mmdit_gr
 
 It IS a `torch.optim.AdamW` (reference model_trainer.py:260-269): same constructor, same `param_groups`, and the same per-parameter
 state (`step` device scalar, `exp_avg`, `exp_avg_sq`) as torch's fused implementation, so `state_dict()` / `load_state_dict()`
-and the reference's `optim.pkl` checkpoints are interchangeable with it and the LR scheduler drives it unchanged.  `step()` is
+and the reference's `optim.pkl` checkpoints are interchangeable with it and the LR scheduler drives it unchanged.  Like torch's, every
+parameter has its OWN step counter and a parameter without a gradient is skipped: the update launch (`mmdit_adamw_step_dlr_pt`,
+include/mmdit_hip_optim.h) reads the counter of each chunk's tensor, so a parameter that gets its first gradient late takes t = 1.  `step()` is
 torch's own; `step_clipped()` is the fused sequence.  There is no CPU fallback: it needs the HIP library and CUDA tensors.
 """
 import ctypes
@@ -61,7 +63,8 @@ class ClipAdamW(torch.optim.AdamW):
         """Device pointer table + chunk map for `groups` = [[(p, g, m, v), ...] per param group].  The chunk map depends only
         on the sizes (built once); the pointer table (40 B per tensor) is re-uploaded whenever a pointer moved -- the gradient
         arenas of the backward pass come from the caching allocator and do move -- through a small ring of pinned staging
-        buffers and an asynchronous copy: no allocation and no host wait in the steady state."""
+        buffers and an asynchronous copy: no allocation and no host wait in the steady state.
+        (The chunk map is RESTATED in tests/test_optim_edges_gpu.py, chunk_map: a change here must be made there as well.)"""
         ptrs = tuple((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), s.data_ptr() if s is not None else 0)
                      for grp in groups for p, g, m, v, s in grp)
         layout = (tuple(len(grp) for grp in groups), tuple(k[4] for k in ptrs), dev)
@@ -176,11 +179,12 @@ class ClipAdamW(torch.optim.AdamW):
         for gi, (group, rows, (c0, c1)) in enumerate(zip(self.param_groups, groups, t["ranges"])):
             if not rows:
                 continue
-            step0 = self.state[rows[0][0]]["step"]
+            # every chunk reads the counter of ITS tensor (steps_flat is in the order of the pointer table): torch keeps `step` per parameter and
+            # skips parameters without a gradient, so the counters of one group differ once a parameter gets its first gradient late or misses a step
             b1, b2 = group["betas"]
-            _lib.check(L.mmdit_adamw_step_dlr(vp(t["tensors"]), ctypes.c_void_p(t["chunk_tensor"].data_ptr() + 4 * c0), ctypes.c_void_p(t["chunk_off"].data_ptr() + 8 * c0), c1 - c0,
-                                              vp(t["out3"]), vp(step0), ctypes.c_void_p(lr_dev.data_ptr() + 8 * gi), float(b1), float(b2), float(group["eps"]),
-                                              float(group["weight_decay"]), s), "mmdit_adamw_step_dlr")
+            _lib.check(L.mmdit_adamw_step_dlr_pt(vp(t["tensors"]), ctypes.c_void_p(t["chunk_tensor"].data_ptr() + 4 * c0), ctypes.c_void_p(t["chunk_off"].data_ptr() + 8 * c0), c1 - c0,
+                                                 vp(t["out3"]), vp(steps_flat), ctypes.c_void_p(lr_dev.data_ptr() + 8 * gi), float(b1), float(b2), float(group["eps"]),
+                                                 float(group["weight_decay"]), s), "mmdit_adamw_step_dlr_pt")
         steps_flat.add_(1.0 - t["out3"][1])
         packing.bump_epoch()     # the kernels wrote the parameters through raw pointers: the bf16 operand copies are stale now ...
         self._last_shadows = (shadow_packs, {id(r[0]) for rows in groups for r in rows if r[4] is not None})

@@ -1427,6 +1427,41 @@ def test_clip_adamw_matches_torch_sequence(ops):
     assert all(float(s["step"]) == 5.0 and s["step"].dim() == 0 for s in sd["state"].values())
 
 
+def test_clip_adamw_keeps_a_step_counter_per_parameter(ops):
+    """torch's fused AdamW keeps `step` per parameter and skips parameters whose .grad is None (zero_grad() sets gradients to None): a parameter
+    that receives its first gradient at step 3, and one that misses step 4, take the bias corrections of THEIR OWN t.  Two param groups, six
+    steps against torch.optim.AdamW(fused=True) on the same gradients; parameters and both moments under the bars of
+    test_clip_adamw_matches_torch_sequence (2e-6 relative), every step counter exact."""
+    from sd3_amd.optim import ClipAdamW
+    shapes = [(7,), (300, 300), (65536 + 3,), (64, 768), (2049,), (5,)]
+    base = [rnd(*s, seed=300 + i) for i, s in enumerate(shapes)]
+    late, gap = 1, 4            # parameter 1 (group 0): no gradient on steps 1-2; parameter 4 (group 1): no gradient on step 4
+
+    def make(cls):
+        ps = [torch.nn.Parameter(b.clone()) for b in base]
+        return ps, cls([dict(params=ps[:3], weight_decay=0.01), dict(params=ps[3:], weight_decay=0.1, lr=3e-4, betas=(0.5, 0.9))], lr=1e-3, betas=(0.9, 0.999), eps=1e-8, fused=True)
+
+    pa, oa = make(ClipAdamW)
+    pb, ob = make(torch.optim.AdamW)
+    for step in range(1, 7):
+        for i, (qa, qb) in enumerate(zip(pa, pb)):
+            if (i == late and step <= 2) or (i == gap and step == 4):
+                qa.grad = qb.grad = None
+                continue
+            g = rnd(*qa.shape, seed=3000 + 10 * step + i) * (0.3 if step % 2 else 1e-3)
+            qa.grad, qb.grad = g.clone(), g.clone()
+        found_inf, _ = oa.step_clipped(None, None)
+        ob.step()
+        assert float(found_inf) == 0.0
+    want = {late: 4.0, gap: 5.0}
+    for i, (qa, qb) in enumerate(zip(pa, pb)):
+        sa, sb = oa.state[qa], ob.state[qb]
+        assert float(sa["step"]) == float(sb["step"]) == want.get(i, 6.0), (i, float(sa["step"]), float(sb["step"]))
+        assert rel(qa, qb) < 2e-6, (i, rel(qa, qb))
+        assert rel(sa["exp_avg"], sb["exp_avg"]) < 2e-6, i
+        assert rel(sa["exp_avg_sq"], sb["exp_avg_sq"]) < 2e-6, i
+
+
 def test_clip_adamw_rewrites_bf16_operand_copies(ops):
     """The update kernel also rewrites the packed bf16 GEMM-operand copy of every parameter that lives in exactly one pack
     (mmdit_adamw_tensor.shadow_bf16): after step_clipped those packs are current without a refresh pass and hold exactly
