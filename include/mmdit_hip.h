@@ -212,9 +212,17 @@ int mmdit_fp8_quantize(const void* x, int x_dtype, int64_t n, const float* amax,
 int mmdit_fp8_quantize_delayed(const void* x, int x_dtype, int64_t n, float* state, int phase, float margin, void* q_fp8, mmdit_stream_t stream);
 /* MX (OCP microscaling) e4m3 quantisation of a row-major operand x[rows][K] (leading dimension ldx, K % 64 == 0):
  * one pass, no state.  Every 32 consecutive K values share the smallest E8M0 scale 2^e with amax / 2^e <= 448 (e = floor(log2 amax) - 8,
- * or one more when the mantissa of amax exceeds 1.75; an all-zero block gets 2^-127); q[rows][K] = saturate_e4m3(x / scale), scales in the layout mmdit_gemm_args.scale_mode 1 reads
+ * or one more when the mantissa of amax exceeds 1.75, e clamped to [-127, 127]: a block with amax <= 448 * 2^-127 = 1.75 * 2^-119 -- all-zero
+ * and denormal blocks included -- gets the smallest scale 2^-127, scale byte 0; input denormals are not flushed); q[rows][K] = saturate_e4m3(x / scale),
+ * round to nearest even, the sign of a zero kept; scales in the layout mmdit_gemm_args.scale_mode 1 reads
  * (allocate (K / 64) * rows_pad128 * 2 + 512 bytes).  Replaces the per-tensor amax / delayed-scaling passes in front of an fp8 GEMM
- * (reference: none -- the reference runs bf16 autocast; BASELINE.json config 5 asks for an fp8 inference path). */
+ * (reference: none -- the reference runs bf16 autocast; BASELINE.json config 5 asks for an fp8 inference path).
+ * Non-finite inputs, all quantisers of this header and their zero-padding forms (what the code does, pinned by tests/test_fp8_quant_edges_gpu.py; no
+ * NaN code 0x7F / 0xFF is ever written): every amax is an fmaxf chain, which ignores a NaN and returns +inf for an inf.  The clamp to +-448 in front of
+ * the converter is fmaxf(., -448) then fminf(., 448): +-inf leaves as the +-448 codes 0x7E / 0xFE and a NaN, of either sign, as 0xFE.  An MX block that
+ * holds an inf gets the scale byte 247 (exponent field 255's e = 120: its finite elements are divided by 2^120 like any others); a NaN leaves its block's
+ * scale alone.  Per tensor, a finite range (a preset amax, the delayed state) scales the finite elements as usual; a range of +inf (mmdit_fp8_amax
+ * of a tensor that holds an inf) gives scale[0] = +inf, factor 0: the finite elements leave as signed zeros and inf * 0 = NaN as 0xFE. */
 int mmdit_mxfp8_quantize(const void* x, int x_dtype, int rows, int K, int64_t ldx, void* q_fp8, void* scales_e8m0, mmdit_stream_t stream);
 /* MX-producing variants of the three kernels whose outputs feed the fp8 GEMMs of a block (inference, "mxfp8" precision): the
  * activation leaves its producer as e4m3 codes + E8M0 block scales (layout and size as for mmdit_gemm_args.scale_mode 1), bit-identical to the bf16 output followed by mmdit_mxfp8_quantize -- no quantise pass in front of the

@@ -12,7 +12,8 @@
  * is zero, the product is exact.  The pad (64 bytes per row when K % 128 == 64, none when K % 128 == 0) is written by the kernel on EVERY
  * call, with ordinary 16-byte vector stores: the caller's buffers may be uninitialised (an unwritten e4m3fn byte can be a NaN code, 0x7F /
  * 0xFF, and an unwritten E8M0 byte the NaN scale 0xFF -- one of them poisons a whole output row of the GEMM).  When K % 128 == 0 the outputs
- * equal the plain entry points' byte for byte.  The arithmetic is the plain quantisers' own (one device header, csrc/fp8_quant.h).
+ * equal the plain entry points' byte for byte.  The arithmetic is the plain quantisers' own (one device header, csrc/fp8_quant.h).  Non-finite
+ * inputs leave as the core header says next to mmdit_mxfp8_quantize.
  *
  * Common argument checks: a NULL pointer, rows <= 0, ldx < K or ldx % 8 != 0 (16-byte row loads): MMDIT_ERR_ARG; K <= 0, K % 64 != 0 or
  * rows * K_pad / 16 beyond INT_MAX: MMDIT_ERR_SHAPE; x_dtype other than MMDIT_BF16 / MMDIT_F32: MMDIT_ERR_DTYPE.

@@ -131,11 +131,16 @@ __device__ __forceinline__ void swiglu_bwd_f(float d, float g, float u, float& d
 }
 
 // ---- MX (OCP microscaling) e4m3 helpers ------------------------------------------------------------------------------------
-// E8M0 exponent of a 32-block with absolute maximum amax: the smallest power of two with amax / 2^ex <= 448 (floor(log2 amax) - 8
-// from the float's exponent field, plus one when the mantissa exceeds 448 / 256; zero / denormal amax -> 2^-127), and 2^-ex.
+// E8M0 exponent of a 32-block with absolute maximum amax >= 0 (never a NaN: fmaxf drops it): the smallest ex in [-127, 127] with
+// amax <= 448 * 2^ex, and 2^-ex.  From the float's bit fields alone: exponent field - 127 - 8, plus one when the mantissa exceeds 1.75 =
+// 448 / 256 (bits 0x600000), clamped -- every amax <= 1.75 * 2^-119 = 448 * 2^-127, zero and the denormals included, gets 2^-127.  (The
+// comparison against a constructed 448 * 2^ex that stood here built 2^-127 from exponent field 0, i.e. 0.0, and gave the amax of exponent
+// field 8 up to mantissa 1.75 the scale 2^-126: one bit lost.  tests/test_fp8_quant_edges_gpu.py walks every exponent field.)
+// +inf has no such ex and gets exponent field 255's, 120 (as it did: 448 * 2^120 overflows to +inf, and inf > inf is false).
 __device__ __forceinline__ int mx_exponent(float amax, float& inv) {
-  int ex = (int)((__float_as_uint(amax) >> 23) & 0xff) - 127 - 8;
-  if (amax > 448.f * __uint_as_float((unsigned)(ex + 127 > 0 ? ex + 127 : 0) << 23)) ex++;
+  const unsigned b = __float_as_uint(amax);
+  int ex = (int)((b >> 23) & 0xff) - 127 - 8;
+  if ((b & 0x7fffffu) > 0x600000u) ex++;
   ex = ex < -127 ? -127 : (ex > 127 ? 127 : ex);
   const unsigned f = (unsigned)(127 - ex) << 23;
   inv = __uint_as_float(f ? f : 0x00400000u);   // (ex = 127: 2^-127 is a denormal)
